@@ -8,7 +8,15 @@ One step = one eval_g and one eval_jac_g of the full NLP at an iterate
 resident in HBM (device-pointer C ABI), results left in HBM.  The calls are
 asynchronous (mh_set_async) on torch's current stream: each returns once its
 kernels are enqueued and the timed region ends with torch.cuda.synchronize()
-(barrier + synchronize on both sides).  Beside the headline:
+(barrier + synchronize on both sides).
+
+A plain run (--gpus 1 --steps K --warmup W) does only what the headline needs:
+it builds the NLP, settles the clocks, runs the W warmup and the K timed
+steps, writes the outputs of the last timed step if --dump-outputs DIR is
+given (DIR/g.npy, DIR/jac_values.npy: the constraint vector and the Jacobian
+values a caller of the timed path finds in its buffers, float64; the iterate
+is seeded, so two builds are compared output for output) and prints the line.
+Everything below is measured only with --full, beside the headline:
   value_fused     the IPOPT eval_g(new_x) -> eval_jac_g(!new_x) pair as one
                   mh_eval_g_jac_g_device call (identical results);
   value_blocking  every call synchronizes before returning (what a blocking
@@ -40,8 +48,8 @@ kernels are enqueued and the timed region ends with torch.cuda.synchronize()
       rank's PCIe link), "replicas" (every rank its own NLP, weak scaling),
       "inverse_solve_sweep" (configs[4]: 64 MocoInverse solves distributed
       over the ranks) and "sharded_solve" (configs[2] solved by one
-      optimizer over all ranks).  The secondary legs run after the headline
-      under try/except and a watchdog (--leg-timeout): a failure lands in
+      optimizer over all ranks).  With --full the secondary legs (replicas,
+      sweep, sharded solve) run after the headline under try/except and a watchdog (--leg-timeout): a failure lands in
       "errors", never loses the line.
   --multi replicas: every rank evaluates its own NLP (independent trials,
       the configs[4] batch layout), no collective on the data path ->
@@ -85,6 +93,13 @@ def parse():
     ap.add_argument("--warmup", type=int, default=1000)
     ap.add_argument("--settle-s", type=float, default=0.3,
                     help="untimed wall time of headline calls before the warmup steps (GPU clock ramp)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline, measure everything else the line can hold (secondary "
+                         "modes and sizes, roofline pass, CPU baselines, batches, solves); a run without "
+                         "it times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one left in the caller's buffers "
+                         "as DIR/g.npy and DIR/jac_values.npy (float64)")
     ap.add_argument("--intervals", type=int, default=200)
     ap.add_argument("--fd", default="forward")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=8.0)
@@ -267,6 +282,22 @@ def measure(cx, step, args, k=None, w=None):
         step()
     k = args.steps if k is None else k
     return k, cx.timed(step, k)
+
+
+DUMP_MAX_ELEMENTS = 4_000_000   # per array (float64): two arrays stay under 64 MB
+
+
+def dump_outputs(directory, arrays):
+    """--dump-outputs: the device buffers the timed path wrote in its last
+    step, as DIR/<name>.npy (float64).  An array longer than
+    DUMP_MAX_ELEMENTS is written as a fixed, seeded sample of its entries
+    (the same entries in every run)."""
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        a = np.ascontiguousarray(t.detach().cpu().numpy(), dtype=np.float64)
+        if a.size > DUMP_MAX_ELEMENTS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMENTS, replace=False))]
+        np.save(os.path.join(directory, name + ".npy"), a)
 
 
 def host_inclusive(cx, nlp, x, args):
@@ -593,7 +624,7 @@ def _mesh_build(args):
             else (lambda: configs.gait10dof18musc(N, fd_scheme=args.fd)))
 
 
-def mesh_measure(cx, args):
+def mesh_measure(cx, args, dump=None):
     """--gpus N > 1, the headline: ONE NLP (the N = 1 headline's workload)
     sharded by mesh interval over the ranks, and per call the north star's
     data path for a single optimizer -- x broadcast from rank 0 over RCCL,
@@ -642,6 +673,8 @@ def mesh_measure(cx, args):
             nlp.eval_jac_g_device(xp, vp)
     settled = settle(cx, step_reassembled, args.settle_s)
     k, el = measure(cx, step_reassembled, args)
+    if dump and cx.rank == 0:
+        dump_outputs(dump, {"g": sg.g[:nlp.m], "jac_values": sg.values[:nlp.nnz]})
     ok = None
     if cx.rank == 0:
         # the reassembled vectors against one unsharded evaluation
@@ -879,7 +912,7 @@ def mesh_main(cx, args):
     import threading
     N = args.intervals
     build = _mesh_build(args)
-    m = mesh_measure(cx, args)
+    m = mesh_measure(cx, args, dump=args.dump_outputs)
     one = one_gpu_reference(cx, args, build)
     line = None
     if cx.rank == 0:
@@ -901,7 +934,7 @@ def mesh_main(cx, args):
         if one is not None:
             line["one_gpu"] = one
             line["strong_scaling"] = round(m["value"] / one["value"], 4)
-    if args.single_mode:
+    if args.single_mode or not args.full:
         if cx.rank == 0:
             print(json.dumps(line), flush=True)
         return
@@ -988,8 +1021,12 @@ def main():
     settled = settle(cx, head, args.settle_s)
     k, elapsed = measure(cx, head, args)
     value = k * cx.world / elapsed
+    if args.dump_outputs and cx.rank == 0:
+        dump_outputs(args.dump_outputs, {"g": gd[:nlp.m], "jac_values": vd[:nlp.nnz]})
     extra = {}
-    if not args.single_mode:
+    # everything below the headline is measured with --full only
+    secondary = args.full and not args.single_mode
+    if secondary:
         other = sep if args.mode == "fused" else fused
         _, el = measure(cx, other, args)
         extra["value_fused" if args.mode == "separate" else "value_separate"] = round(k * cx.world / el, 3)
@@ -997,9 +1034,11 @@ def main():
         _, el = measure(cx, head, args)
         extra["value_blocking"] = round(k * cx.world / el, 3)
         nlp.set_async(not args.blocking)
-    roof = roofline(cx, nlp, (sep, fused, (xd.data_ptr(), gd.data_ptr()), (xd.data_ptr(), vd.data_ptr())),
-                    args, args.mode)
-    if not args.single_mode:
+    roof = None
+    if args.full:
+        roof = roofline(cx, nlp, (sep, fused, (xd.data_ptr(), gd.data_ptr()), (xd.data_ptr(), vd.data_ptr())),
+                        args, args.mode)
+    if secondary:
         # the north-star size
         st4 = configs.gait10dof18musc(400, fd_scheme=args.fd)
         n4 = make_nlp(cx, st4, blocking=args.blocking)
@@ -1079,11 +1118,11 @@ def main():
             invb["workload"] = inv["workload"]
             extra["inverse_batched"] = invb
     mesh = None
-    if cx.world > 1 and not args.single_mode:
+    if cx.world > 1 and secondary:
         mesh = mesh_measure(cx, args)
     if cx.rank == 0:
         cpu = cpu1 = None
-        if cx.world == 1 and not args.no_cpu_baseline:
+        if args.full and cx.world == 1 and not args.no_cpu_baseline:
             box = int(os.environ.get("OMP_NUM_THREADS", "0") or 0) or min(16, os.cpu_count() or 1)
             threads = max(1, min(box, os.cpu_count() or 1))
             cpu = cpu_baseline(nlp.rep, st.solver.options(), x, args.cpu_baseline_seconds, threads)
@@ -1095,7 +1134,7 @@ def main():
             "steps": k, "warmup": args.warmup, "settle_s": settled,
             "ms_per_step": round(1e3 * elapsed / k, 5), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f64",
-            "data": "synthetic",
+            "data": "synthetic", "full": bool(args.full),
             "config": {"workload": "MocoTrack gait10dof18musc DGF rigid tendon (configs[2])",
                        "mesh_intervals": N, "grid_points": nlp.G, "n": nlp.n, "m": nlp.m,
                        "nnz_jac": nlp.nnz, "transcription": "hermite-simpson",

@@ -15,7 +15,7 @@ for rep in 1 2; do
     for setting in "$@"; do
         envs=()
         [ "$setting" != "-" ] && read -r -a envs <<< "$setting"
-        env "${envs[@]}" timeout -k 10 200 python3 "$ROOT/bench.py" --single-mode --no-cpu-baseline \
+        env "${envs[@]}" timeout -k 10 200 python3 "$ROOT/bench.py" --full --single-mode --no-cpu-baseline \
             > "$OUT/bench_${i}_$rep.log" 2>&1
         echo "$setting" > "$OUT/setting_$i.txt"
         i=$((i + 1))

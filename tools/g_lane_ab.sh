@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/g_lane
 mkdir -p "$OUT"
 cd "$ROOT"
 for gl in 0 1; do
-    MOCOHIP_G_LANE=$gl timeout -k 10 300 python bench.py --single-mode --no-cpu-baseline \
+    MOCOHIP_G_LANE=$gl timeout -k 10 300 python bench.py --full --single-mode --no-cpu-baseline \
         > "$OUT/gl$gl.json" 2>> "$OUT/err.log"
     echo "g_lane $gl: $(python -c "import json;d=json.load(open('$OUT/gl$gl.json'));print(d['value'], d['roofline'].get('eval_g_stage_ms'))")"
 done

@@ -19,10 +19,10 @@ for what in "$@"; do
         timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
         tail -2 "$OUT/smoke.log";;
     bench)
-        timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+        timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
         timeout -k 10 120 python tools/driver_bench.py 200 > "$OUT/driver.json" 2> "$OUT/driver.err" || true;;
     mesh)
-        timeout -k 10 300 python bench.py --multi mesh --steps 500 --warmup 200 > "$OUT/mesh.json" 2> "$OUT/mesh.err"
+        timeout -k 10 300 python bench.py --full --multi mesh --steps 500 --warmup 200 > "$OUT/mesh.json" 2> "$OUT/mesh.err"
         tail -1 "$OUT/mesh.json";;
     phases)
         timeout -k 10 600 bash tools/iv_phases.sh "$TAG" 200;;

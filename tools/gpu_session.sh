@@ -20,7 +20,7 @@ if [[ $WHAT == tests || $WHAT == all || $WHAT == final ]]; then
     timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1
 fi
 if [[ $WHAT == bench || $WHAT == all ]]; then
-    timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+    timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
     timeout -k 10 120 python tools/driver_bench.py 200 > "$OUT/driver.json" 2> "$OUT/driver.err"
 fi
 if [[ $WHAT == profile || $WHAT == all || $WHAT == final ]]; then
@@ -33,6 +33,6 @@ d = json.load(open(sys.argv[1]))
 d["source"] = f"profiles/{sys.argv[2]}/pmc.json"
 json.dump(d, open("profiles/pmc_current.json", "w"), indent=1)
 PY
-    timeout -k 10 300 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err"
+    timeout -k 10 300 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err"
 fi
 echo "session $TAG done"

@@ -13,13 +13,13 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for rep in 1 2; do
     for v in 0 1; do
-        MOCOHIP_GROUPS_XCD=$v timeout -k 10 200 python3 "$ROOT/bench.py" --single-mode --no-cpu-baseline \
+        MOCOHIP_GROUPS_XCD=$v timeout -k 10 200 python3 "$ROOT/bench.py" --full --single-mode --no-cpu-baseline \
             > "$OUT/bench_xcd${v}_$rep.log" 2>&1
     done
 done
 for v in 0 1; do
     MOCOHIP_GROUPS_XCD=$v timeout -s KILL 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d "$OUT/fetch$v" -o run \
-        -- python3 "$ROOT/bench.py" --steps 50 --warmup 5 --no-cpu-baseline --single-mode --mode fused \
+        -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline --single-mode --mode fused \
         > "$OUT/fetch$v.log" 2>&1
 done
 python3 - "$OUT" <<'PY' | tee "$OUT/summary.txt"

@@ -12,10 +12,10 @@ i=0
 for V in "$@"; do
     for N in 200 400; do
         env $V timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv \
-            -d "$OUT/v${i}_n$N" -o run -- python3 "$ROOT/bench.py" --steps 100 --warmup 20 --no-cpu-baseline \
+            -d "$OUT/v${i}_n$N" -o run -- python3 "$ROOT/bench.py" --full --steps 100 --warmup 20 --no-cpu-baseline \
             --single-mode --mode fused --intervals "$N" > "$OUT/v${i}_n$N.log" 2>&1
     done
-    env $V timeout -k 10 300 python3 "$ROOT/bench.py" --no-cpu-baseline > "$OUT/v${i}_bench.json" 2> "$OUT/v${i}_bench.err"
+    env $V timeout -k 10 300 python3 "$ROOT/bench.py" --full --no-cpu-baseline > "$OUT/v${i}_bench.json" 2> "$OUT/v${i}_bench.err"
     echo "$i: $V" >> "$OUT/variants.txt"
     i=$((i+1))
 done

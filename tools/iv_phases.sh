@@ -16,20 +16,20 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 # the Jacobian through k_interval whole, without the assembly-word prefetch
 MOCOHIP_IV_PF=0 timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv \
-    -d "$OUT/noroles" -o run -- python3 "$ROOT/bench.py" --steps 50 --warmup 5 --no-cpu-baseline \
+    -d "$OUT/noroles" -o run -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline \
     --single-mode --mode fused --intervals "$N" > "$OUT/noroles.log" 2>&1
 for t in 256 c0; do
     (
     export MOCOHIP_ROLES=1
     if [ "$t" = c0 ]; then export MOCOHIP_ROLE_COUPLE=0; else export MOCOHIP_ROLE_THREADS=$t; fi
     timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/roles$t" -o run -- python3 "$ROOT/bench.py" --steps 50 --warmup 5 --no-cpu-baseline \
+        -d "$OUT/roles$t" -o run -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline \
         --single-mode --mode fused --intervals "$N" > "$OUT/roles$t.log" 2>&1
     )
 done
 for s in 0 7 1 2 3 4 5 6; do
     MOCOHIP_IV_DEBUG_STOP=$s timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv \
-        -d "$OUT/stop$s" -o run -- python3 "$ROOT/bench.py" --steps 50 --warmup 5 --no-cpu-baseline \
+        -d "$OUT/stop$s" -o run -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline \
         --single-mode --mode fused --intervals "$N" > "$OUT/stop$s.log" 2>&1
 done
 python3 "$ROOT/tools/kstats.py" "$OUT" > "$OUT/summary.txt"

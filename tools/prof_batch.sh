@@ -15,7 +15,7 @@ timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/
 MOCOHIP_BATCH_GM=0 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/lds" -o run \
     -- python3 $B > "$OUT/lds.log" 2>&1
 timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/single" -o run \
-    -- python3 $ROOT/bench.py --steps 200 --warmup 50 --no-cpu-baseline --single-mode --mode fused \
+    -- python3 $ROOT/bench.py --full --steps 200 --warmup 50 --no-cpu-baseline --single-mode --mode fused \
     > "$OUT/single.log" 2>&1
 python3 "$ROOT/tools/kstats.py" "$OUT" > "$OUT/summary.txt"
 cat "$OUT/summary.txt"

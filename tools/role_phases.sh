@@ -15,7 +15,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for s in 0 1 2 3 4; do
     MOCOHIP_ROLE_THREADS=$TH MOCOHIP_IV_DEBUG_STOP=$s timeout -k 10 180 rocprofv3 --kernel-trace --stats \
-        --output-format csv -d "$OUT/stop$s" -o run -- python3 "$ROOT/bench.py" --steps 50 --warmup 5 \
+        --output-format csv -d "$OUT/stop$s" -o run -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 \
         --no-cpu-baseline --single-mode --mode fused --intervals "$N" > "$OUT/stop$s.log" 2>&1
 done
 python3 "$ROOT/tools/kstats.py" "$OUT" > "$OUT/summary.txt"

@@ -12,10 +12,10 @@
 #   parity:<expr>    tests/test_gpu_parity.py -k <expr>
 #   smoke            __graft_entry__.smoke()
 #   bench            the default bench line (bench.json)
-#   bench20          bench.py --steps 20 --warmup 5
+#   bench20          bench.py --full --steps 20 --warmup 5
 #   driver           the C++ host's calls/s (tools/driver_bench.py 200)
 #   shard            bench.py --shard-model (the multi-GPU model's shard timings)
-#   mesh1            bench.py --multi mesh at world 1 (the mesh path's code)
+#   mesh1            bench.py --full --multi mesh at world 1 (the mesh path's code)
 #   profile          tools/profile_gpu.sh (kernel trace + PMC passes, pmc.json)
 #   pmcsrc           point pmc.json's "source" at profiles/<tag>/pmc.json
 #   ifetch           instruction-fetch PMC pass of eval_g (separate mode)
@@ -43,13 +43,13 @@ for step in "$@"; do
     parity:*) timeout -k 10 900 $PYT tests/test_gpu_parity.py -v -k "${step#parity:}" \
                > "$OUT/pytest_parity.log" 2>&1 || exit $? ;;
     smoke) timeout -k 10 200 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke.log" 2>&1 || exit $? ;;
-    bench) timeout -k 10 400 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $? ;;
-    bench20) timeout -k 10 300 python bench.py --steps 20 --warmup 5 > "$OUT/bench20.json" 2> "$OUT/bench20.err" \
+    bench) timeout -k 10 400 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || exit $? ;;
+    bench20) timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > "$OUT/bench20.json" 2> "$OUT/bench20.err" \
                || exit $? ;;
     driver) timeout -k 10 120 python tools/driver_bench.py 200 > "$OUT/driver.json" 2> "$OUT/driver.err" || exit $? ;;
     shard) timeout -k 10 300 python bench.py --shard-model --steps 1000 --warmup 500 > "$OUT/shard_model.json" \
                2> "$OUT/shard_model.err" || exit $? ;;
-    mesh1) timeout -k 10 300 python bench.py --multi mesh --steps 500 --warmup 200 --sweep 8 > "$OUT/mesh1.json" \
+    mesh1) timeout -k 10 300 python bench.py --full --multi mesh --steps 500 --warmup 200 --sweep 8 > "$OUT/mesh1.json" \
                2> "$OUT/mesh1.err" || exit $? ;;
     profile) timeout -k 10 900 bash tools/profile_gpu.sh "$TAG" > "$OUT/profile.log" 2>&1 || exit $? ;;
     pmcsrc) python - "gpurun_out/prof_$TAG/pmc.json" "$TAG" <<'PY' || exit $?
@@ -62,7 +62,7 @@ PY
     ifetch) mkdir -p "gpurun_out/prof_$TAG"
         ( cd /tmp && export TMPDIR=/tmp && timeout -s KILL 120 rocprofv3 --pmc SQC_TC_INST_REQ SQC_ICACHE_MISSES \
             SQC_ICACHE_REQ SQ_WAVES TCC_HIT TCC_MISS --output-format csv -d "$ROOT/gpurun_out/prof_$TAG/pmc_ifetch_sep" \
-            -o run -- python3 "$ROOT/bench.py" --steps 50 --warmup 5 --no-cpu-baseline --single-mode --mode separate \
+            -o run -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline --single-mode --mode separate \
             > "$ROOT/gpurun_out/prof_$TAG/pmc_ifetch_sep.log" 2>&1 ) || exit $? ;;
     counters) ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 120 rocprofv3 --list-avail ) > "$OUT/counters.txt" 2>&1 \
                || exit $? ;;

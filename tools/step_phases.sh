@@ -16,7 +16,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 for s in 0 7 1 2 4; do
     MOCOHIP_IV_DEBUG_STOP=$s timeout -k 10 180 rocprofv3 --kernel-trace --output-format csv \
-        -d "$OUT/stop$s" -o run -- python3 "$ROOT/bench.py" --steps 200 --warmup 20 --no-cpu-baseline \
+        -d "$OUT/stop$s" -o run -- python3 "$ROOT/bench.py" --full --steps 200 --warmup 20 --no-cpu-baseline \
         --single-mode --mode separate --intervals "$N" > "$OUT/stop$s.log" 2>&1
 done
 python3 "$ROOT/tools/step_stats.py" "$OUT" > "$OUT/summary.txt"
