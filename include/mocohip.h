@@ -349,13 +349,37 @@ typedef struct mh_goal {
  * `column` of model table `table` (Constant: table = -1, `value`).  Each
  * equation's Jacobian row is block-dense over t0, tf and the mesh point's
  * inputs, and its values are the finite-difference quotients of the
- * path-constraint function, as for the DAE outputs. */
-enum mh_path_kind { MH_PATH_CONTROL_BOUND = 0 };
+ * path-constraint function, as for the DAE outputs.
+ *
+ * A MocoFrameDistanceConstraint (MocoFrameDistanceConstraint.cpp:56-136)
+ * expands to one equation per frame pair, in order:
+ *     r = p_G(frame 2) - p_G(frame 1)      (positions in ground at the mesh
+ *                                           point's coordinates)
+ *     MH_PATH_FRAME_DISTANCE         e = r
+ *     MH_PATH_FRAME_DISTANCE_VECTOR  e = (r . n) n
+ *     MH_PATH_FRAME_DISTANCE_PLANE   e = r - (r . n) n
+ *     error = e . e,  g bounds [minimum^2, maximum^2]
+ * `index` = frame 1's body (mh_model body index, -1 = ground), `table` =
+ * frame 2's body, `column` = a term offset into mh_problem.goal_weight, where
+ * nine doubles follow: frame 1's location in its body (x, y, z), frame 2's
+ * location in its body, the unit projection vector n (zeros for
+ * MH_PATH_FRAME_DISTANCE).  Those terms belong to no goal (their goal_index /
+ * goal_column slots are 0; nterms counts them); `value` is unused.  The
+ * equation reads only the coordinate values: its quotients along every other
+ * input, and along coordinates off both frames' ancestor chains, are exactly
+ * 0.  Needs coordinate states (no prescribed kinematics), nq <= 64, and is
+ * not served by mh_batch_*. */
+enum mh_path_kind {
+    MH_PATH_CONTROL_BOUND = 0,
+    MH_PATH_FRAME_DISTANCE = 1,
+    MH_PATH_FRAME_DISTANCE_VECTOR = 2,
+    MH_PATH_FRAME_DISTANCE_PLANE = 3
+};
 typedef struct mh_path_equation {
     int32_t kind;        /* mh_path_kind                                   */
-    int32_t index;       /* control index                                  */
-    int32_t table;       /* bound function: model table, -1 = constant     */
-    int32_t column;      /* table column                                   */
+    int32_t index;       /* control index / frame 1's body                 */
+    int32_t table;       /* bound function: model table, -1 = constant / frame 2's body */
+    int32_t column;      /* table column / term offset of the nine doubles */
     double value;        /* constant bound (table = -1)                    */
     mh_bounds g;         /* bounds on the constraint row                   */
 } mh_path_equation;
@@ -729,6 +753,13 @@ int mh_batch_set_group_results_global(mh_batch* batch, int global_memory);
  * (implicit: [multibody residual(NQ), zdot(NZ)]) per point.  Used by
  * parity tests. */
 int mh_eval_dae(mh_ctx* ctx, int32_t npoints, const double* inputs,
+        double* outputs);
+/* Path-constraint probe, the counterpart of mh_eval_dae for the path
+ * callback: the npath path-equation values of npoints probe rows [time, point
+ * inputs (NS + NC + NDV + ...)] (the row of mh_get_callback_sparsity, W
+ * doubles), by the device functions the constraint rows use; outputs
+ * [npoints][npath].  Used by parity tests. */
+int mh_eval_path(mh_ctx* ctx, int32_t npoints, const double* inputs,
         double* outputs);
 
 /* Identity of the device back end serving this context: the generic DAE

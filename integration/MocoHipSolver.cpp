@@ -35,6 +35,7 @@
 #include <OpenSim/Moco/MocoGoal/MocoSumSquaredStateGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoGoal.h>
 #include <OpenSim/Moco/MocoControlBoundConstraint.h>
+#include <OpenSim/Moco/MocoFrameDistanceConstraint.h>
 #include <OpenSim/Moco/MocoProblemRep.h>
 #include <OpenSim/Moco/MocoUtilities.h>
 #include <OpenSim/Simulation/Model/ExternalForce.h>
@@ -499,9 +500,44 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
     };
     for (int i = 0; i < rep.getNumCosts(); ++i) addGoal(rep.getCostByIndex(i));
     for (int i = 0; i < rep.getNumEndpointConstraints(); ++i) addGoal(rep.getEndpointConstraintByIndex(i));
-    // path constraints (MocoControlBoundConstraint only)
+    // path constraints: MocoControlBoundConstraint and MocoFrameDistanceConstraint,
+    // in the problem's order
     for (int i = 0; i < rep.getNumPathConstraints(); ++i) {
         const MocoPathConstraint& pc = rep.getPathConstraintByIndex(i);
+        if (const auto* fdc = dynamic_cast<const MocoFrameDistanceConstraint*>(&pc)) {
+            // each frame as an offset frame of its base frame (a body or
+            // ground) under the frame's own path: only its origin matters;
+            // mhb::make_rep runs initializeOnModelImpl's checks
+            mhb::FrameDistanceConstraint hc;
+            hc.name = fdc->getName();
+            hc.projection = fdc->get_projection();
+            if (!fdc->getProperty_projection_vector().empty())
+                for (int d = 0; d < 3; ++d) hc.projection_vector.push_back(fdc->get_projection_vector()[d]);
+            const auto& pairs = fdc->getProperty_frame_pairs();
+            for (int k = 0; k < pairs.size(); ++k) {
+                const MocoFrameDistanceConstraintPair& fp = pairs.getValue(k);
+                mhb::FrameDistancePair hp;
+                hp.frame1_path = fp.get_frame1_path();
+                hp.frame2_path = fp.get_frame2_path();
+                hp.minimum_distance = fp.get_minimum_distance();
+                hp.maximum_distance = fp.get_maximum_distance();
+                for (const std::string& path : {hp.frame1_path, hp.frame2_path}) {
+                    if (!model.hasComponent<Frame>(path)) continue;   // make_rep: "Could not find frame"
+                    const Frame& f = model.getComponent<Frame>(path);
+                    const Frame& base = f.findBaseFrame();
+                    const SimTK::Vec3 loc = f.findTransformInBaseFrame().p();
+                    mhb::OffsetFrame of;
+                    of.name = path;
+                    of.path = path;
+                    of.body = &base == &model.getGround() ? "ground" : base.getName();
+                    for (int d = 0; d < 3; ++d) of.translation[d] = loc[d];
+                    prob.model.add_offset_frame(of);
+                }
+                hc.frame_pairs.push_back(hp);
+            }
+            prob.add_path_constraint(hc);
+            continue;
+        }
         const auto* cb = dynamic_cast<const MocoControlBoundConstraint*>(&pc);
         OPENSIM_THROW_IF(!cb, Exception, "MocoHipSolver: path constraint '{}' of type '{}' is not supported",
                 pc.getName(), pc.getConcreteClassName());
@@ -511,7 +547,7 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
         if (cb->hasLowerBound()) hc.lower = toBoundFunction(cb->getLowerBound());
         if (cb->hasUpperBound()) hc.upper = toBoundFunction(cb->getUpperBound());
         hc.equality_with_lower = cb->getEqualityWithLower();
-        prob.path_constraints.push_back(hc);
+        prob.add_path_constraint(hc);
     }
     // MocoParameters in createParameterNames order (the x layout's last
     // block); mhb::make_rep resolves the component paths and properties and

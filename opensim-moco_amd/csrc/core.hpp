@@ -783,6 +783,36 @@ __global__ void __launch_bounds__(MAXT) k_combine(DevModel M, Src S, Lanes Ln, T
 
 // Path-constraint equations (include/mocohip.h mh_path_equation) and the
 // tables / grid their bound functions and time seeds read.
+// Frame-distance equations (MH_PATH_FRAME_DISTANCE*): k_frame_distance
+// evaluates them per (mesh point, lane) into pf, and the constraint rows and
+// their Jacobian entries read pf.  Lane 0 is the unperturbed point; lane
+// 1 + l moves coordinate coord[l] by +h (backward differences: -h), and for
+// central differences lane 1 + nlc + l moves it by -h.  Only coordinates on
+// the ancestor chain of a body some equation names have lanes.
+// tab (ints): [2 npc] slot of frame 1 / frame 2's body per equation (-1:
+// ground, or another kind), [2 nslots] begin / count of each slot's chain in
+// the body list, [nq] lane index l of each coordinate (-1: off every chain),
+// [nlc] coordinate of lane l, then the chains' bodies, root first.
+struct FrameDist {
+    const double* __restrict__ terms;   // mh_problem.goal_weight
+    double* __restrict__ pf;            // [(mesh point of the shard, lane), equation]
+    const int* __restrict__ tab;
+    int nslots;      // distinct bodies named by the equations (0: no such equation)
+    int nlc;         // coordinates with lanes
+    int nl;          // lanes per mesh point: 1 + nlc (central: 1 + 2 nlc)
+    int nq;
+    int k0, kshift;  // mesh point of grid point k: (k - k0) >> kshift
+    __device__ __forceinline__ const int* slot(int npc) const { return tab; }
+    __device__ __forceinline__ const int* chain(int npc) const { return tab + 2 * npc; }
+    __device__ __forceinline__ const int* lane(int npc) const { return tab + 2 * npc + 2 * nslots; }
+    __device__ __forceinline__ const int* coord(int npc) const { return lane(npc) + nq; }
+    __device__ __forceinline__ const int* bodies(int npc) const { return coord(npc) + nlc; }
+    // pf index of (grid point k, lane, equation e)
+    __device__ __forceinline__ long at(int npc, int k, int ln, int e) const {
+        return ((long)((k - k0) >> kshift) * nl + ln) * npc + e;
+    }
+};
+
 struct PathEqs {
     int npc;         // equations per mesh point
     const mh_path_equation* __restrict__ eq;
@@ -790,6 +820,7 @@ struct PathEqs {
     const double* __restrict__ brk;
     const double* __restrict__ coef;
     const double* __restrict__ grid;
+    FrameDist F;
 };
 
 // Endpoint-constraint equations (include/mocohip.h mh_endpoint_equation):
@@ -951,6 +982,38 @@ __device__ __forceinline__ double path_quot(const PathEqs& P, const Lanes& Ln, i
     return (v0 - (cm - path_bound(P, E, tm))) / h;
 }
 
+// A frame-distance equation's quotient along direction dir from
+// k_frame_distance's lanes, with the three formulas of path_quot.  Without a
+// lane (time, a non-coordinate input, a coordinate off both chains) the
+// perturbed and base values are equal: exactly 0.
+__device__ __forceinline__ double frame_quot(const PathEqs& P, const Lanes& Ln, int e, int k, int dir) {
+#pragma clang fp contract(off)
+    const FrameDist& F = P.F;
+    if (dir < 2 || dir >= 2 + F.nq) return 0.0;
+    const int l = F.lane(P.npc)[dir - 2];
+    if (l < 0) return 0.0;
+    const double h = Ln.h;
+    const double v1 = F.pf[F.at(P.npc, k, 1 + l, e)];
+    if (Ln.fd == MH_FD_CENTRAL) return (v1 - F.pf[F.at(P.npc, k, 1 + F.nlc + l, e)]) / (2.0 * h);
+    const double v0 = F.pf[F.at(P.npc, k, 0, e)];
+    if (Ln.fd == MH_FD_FORWARD) return (v1 - v0) / h;
+    return (v0 - v1) / h;
+}
+// Row value / Jacobian quotient of path equation e at grid point k, by kind.
+template <class YV>
+__device__ __forceinline__ double path_row(const PathEqs& P, const YV& Y, int e, int k) {
+    const mh_path_equation E = P.eq[e];
+    if (E.kind != MH_PATH_CONTROL_BOUND) return P.F.pf[P.F.at(P.npc, k, 0, e)];
+    return path_value(P, e, Y.t(k), Y.xc(k, E.index));
+}
+template <class YV>
+__device__ __forceinline__ double path_jac(const PathEqs& P, const Lanes& Ln, int NS, const YV& Y, int e, int k,
+        int dir) {
+    const mh_path_equation E = P.eq[e];
+    if (E.kind != MH_PATH_CONTROL_BOUND) return frame_quot(P, Ln, e, k, dir);
+    return path_quot(P, Ln, NS, e, k, Y.t(k), Y.xc(k, E.index), dir);
+}
+
 // x index of endpoint input si (initial / final grid point, see EndpointEqs).
 __device__ __forceinline__ long ep_xindex(const Layout& L, int W, int si) {
     const int pt = si >= W ? 1 : 0, j = si - pt * W - 1;
@@ -1077,13 +1140,13 @@ __device__ __forceinline__ double defect_row(const Layout& L, const Interval& I,
         const int kl = k_first + npres;
         if (rt < I.nkr) return Y.row(kl, I.okc + rt)[Ln.base];
         rt -= I.nkr;
-        if (rt < npc) return path_value(I.P, rt, Y.t(kl), Y.xc(kl, I.P.eq[rt].index));
+        if (rt < npc) return path_row(I.P, Y, rt, kl);
         return Y.row(kl, I.rout(rt - npc))[Ln.base];
     }
     // the mesh point's kinematic-constraint rows (callback outputs okc..)
     if (r < I.nkr) return Y.row(k_first, I.okc + r)[Ln.base];
     r -= I.nkr;
-    if (r < npc) return path_value(I.P, r, Y.t(k_first), Y.xc(k_first, I.P.eq[r].index));
+    if (r < npc) return path_row(I.P, Y, r, k_first);
     r -= npc;
     if (r < npres * I.nres) return Y.row(k_first + r / I.nres, I.rout(r % I.nres))[Ln.base];
     r -= npres * I.nres;
@@ -1221,7 +1284,7 @@ __device__ __forceinline__ double jac_entry(const Layout& L, const Lanes& Ln, co
     case T_PATH:
         if constexpr (WITH_PATH) {
             const int k = k_first + T.pt;
-            v = path_quot(P, Ln, L.NS, s, k, Y.t(k), Y.xc(k, P.eq[s].index), dir);
+            v = path_jac(P, Ln, L.NS, Y, s, k, dir);
         }
         break;
     case T_TRAP_T: {
@@ -2176,6 +2239,11 @@ struct mh_ctx {
     std::vector<uint8_t> sp, sp_pc;  // detected sparsity [output][time, inputs] (empty: dense)
     std::vector<mh_path_equation> pc;
     PathEqs P{};
+    // frame-distance equations (FrameDist): the int table as uploaded and the
+    // dynamic LDS of k_frame_distance's poses at all lanes
+    bool has_fdist = false;
+    std::vector<int> fd_tab;
+    size_t fd_lds = 0;
     // goals as uploaded: the problem's, then the internal multiplier term
     std::vector<mh_goal> goals;
     std::vector<int32_t> gidx, gcol;

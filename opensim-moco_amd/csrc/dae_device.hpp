@@ -193,7 +193,10 @@ __device__ __forceinline__ void simm_eval(const DevModel& M, const mh_function& 
     d2 = 2.0 * c[k] + 6.0 * dx * d[k];
 }
 
-__device__ __forceinline__ void fn_eval(const DevModel& M, int f, const double* q, double& v,
+// q: the coordinates, anything indexable (an array, or an accessor that
+// applies a lane's perturbation on the fly: QLane, core.hpp)
+template <class Q>
+__device__ __forceinline__ void fn_eval(const DevModel& M, int f, const Q& q, double& v,
         double& d1, double& d2) {
     const mh_function F = M.funcs[f];
     if (F.kind == MH_FN_CONSTANT) { v = F.a; d1 = 0; d2 = 0; return; }

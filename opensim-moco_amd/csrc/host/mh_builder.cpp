@@ -80,6 +80,28 @@ void Model::add_spring(SpringGeneralizedForce f) {
     if (f.path.empty()) f.path = "/forceset/" + f.name;
     springs.push_back(std::move(f));
 }
+void Model::add_offset_frame(OffsetFrame f) {
+    if (f.body != "ground" && !body(f.body)) fail("offset frame '" + f.name + "': no body '" + f.body + "'");
+    if (f.path.empty()) f.path = (f.body == "ground" ? "/ground/" : "/bodyset/" + f.body + "/") + f.name;
+    for (auto& x : offset_frames)
+        if (x.path == f.path) { x = std::move(f); return; }
+    offset_frames.push_back(std::move(f));
+}
+
+bool Model::find_frame(const std::string& path, std::string& body_name, double location[3]) const {
+    location[0] = location[1] = location[2] = 0.0;
+    if (path == "/ground" || path == "ground") { body_name = "ground"; return true; }
+    for (auto& b : bodies)
+        if (path == b.name || path == "/bodyset/" + b.name) { body_name = b.name; return true; }
+    for (auto& f : offset_frames)
+        if (path == f.path || path == f.name) {
+            body_name = f.body;
+            for (int c = 0; c < 3; ++c) location[c] = f.translation[c];
+            return true;
+        }
+    return false;
+}
+
 void Model::add_marker(Marker m) {
     if (m.path.empty()) m.path = "/markerset/" + m.name;
     for (auto& x : markers)
@@ -438,14 +460,77 @@ std::string num(double v) {
 // MocoControlBoundConstraint path equations (problem.py _path_equations,
 // MocoControlBoundConstraint.cpp:38-118); bound functions other than
 // Constant become tables appended after the model's
-void path_equations(const Problem& P, std::vector<mh_path_equation>& eqs, std::vector<Table>& tables) {
+// What a frame-distance equation still needs once the model is compiled:
+// the two bodies and its nine terms (include/mocohip.h mh_path_kind).
+struct FrameTerms {
+    std::string body1, body2;
+    double terms[9];
+};
+
+// MocoFrameDistanceConstraint::initializeOnModelImpl
+// (MocoFrameDistanceConstraint.cpp:56-112; problem.py
+// _frame_distance_equations): its checks and messages, bounds [minimum^2,
+// maximum^2], one equation per pair.
+void frame_distance_equations(const Model& model, const FrameDistanceConstraint& pc,
+        std::vector<mh_path_equation>& eqs, std::vector<FrameTerms>& frame_terms) {
+    std::vector<FrameTerms> found;
+    for (auto& pair : pc.frame_pairs) {
+        FrameTerms ft{};
+        if (!model.find_frame(pair.frame1_path, ft.body1, ft.terms))
+            fail("Could not find frame '" + pair.frame1_path + "'.");
+        if (!model.find_frame(pair.frame2_path, ft.body2, ft.terms + 3))
+            fail("Could not find frame '" + pair.frame2_path + "'.");
+        const double lo = pair.minimum_distance, hi = pair.maximum_distance;
+        if (lo < 0)
+            fail("Expected the minimum distance for this frame pair to non-negative, but it is " + num(lo) + ".");
+        if (hi < 0)
+            fail("Expected the maximum distance for this frame pair to non-negative, but it is " + num(hi) + ".");
+        if (lo > hi)
+            fail("Expected the minimum distance for this frame pair to be less than or equal to the maximum "
+                 "distance, but they are " + num(lo) + " and " + num(hi) + ", respectively.");
+        found.push_back(ft);
+    }
+    int kind = MH_PATH_FRAME_DISTANCE;
+    if (pc.projection == "vector") kind = MH_PATH_FRAME_DISTANCE_VECTOR;
+    else if (pc.projection == "plane") kind = MH_PATH_FRAME_DISTANCE_PLANE;
+    else if (pc.projection != "none")
+        fail("Expected 'projection' to be 'none', 'vector', or 'plane', but got '" + pc.projection + "'.");
+    double n[3] = {0, 0, 0};
+    if (kind != MH_PATH_FRAME_DISTANCE) {
+        if (pc.projection_vector.size() != 3) fail("Must provide a value for 'projection_vector'.");
+        const double* d = pc.projection_vector.data();
+        if (d[0] == 0.0 && d[1] == 0.0 && d[2] == 0.0) fail("'projection_vector' must not be the zero vector.");
+        const double len = std::sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);   // SimTK::UnitVec3
+        for (int c = 0; c < 3; ++c) n[c] = d[c] / len;
+    }
+    for (size_t i = 0; i < found.size(); ++i) {
+        mh_path_equation e{};
+        e.kind = kind;
+        e.index = e.table = -1;   // the bodies and the term offset: make_rep
+        e.g.lower = pc.frame_pairs[i].minimum_distance * pc.frame_pairs[i].minimum_distance;
+        e.g.upper = pc.frame_pairs[i].maximum_distance * pc.frame_pairs[i].maximum_distance;
+        eqs.push_back(e);
+        for (int c = 0; c < 3; ++c) found[i].terms[6 + c] = n[c];
+        frame_terms.push_back(found[i]);
+    }
+}
+
+void path_equations(const Problem& P, std::vector<mh_path_equation>& eqs, std::vector<Table>& tables,
+        std::vector<FrameTerms>& frame_terms) {
     const auto names = P.model.control_names();
     auto cidx = [&](const std::string& n) {
         auto it = std::find(names.begin(), names.end(), n);
         return it == names.end() ? -1 : (int)(it - names.begin());
     };
-    for (size_t ci = 0; ci < P.path_constraints.size(); ++ci) {
-        const auto& pc = P.path_constraints[ci];
+    if (P.path_order.size() != P.path_constraints.size() + P.frame_distance_constraints.size())
+        fail("path constraints must be added with Problem::add_path_constraint");
+    for (size_t ci = 0; ci < P.path_order.size(); ++ci) {
+        if (P.path_order[ci].first) {
+            frame_distance_equations(P.model, P.frame_distance_constraints[P.path_order[ci].second], eqs,
+                    frame_terms);
+            continue;
+        }
+        const auto& pc = P.path_constraints[P.path_order[ci].second];
         const bool has_lo = pc.lower.kind != BoundFunction::NONE, has_up = pc.upper.kind != BoundFunction::NONE;
         if (!pc.control_paths.empty() && !(has_lo || has_up)) continue;   // the reference warns
         for (auto& path : pc.control_paths)
@@ -603,7 +688,8 @@ void make_rep(const Problem& P, ProblemRep& R) {
     const Model& model = P.model;
     std::vector<mh_path_equation> path_eqs;
     std::vector<Table> extra;
-    path_equations(P, path_eqs, extra);
+    std::vector<FrameTerms> frame_terms;
+    path_equations(P, path_eqs, extra, frame_terms);
     const std::vector<Table> bound_tables = extra;
     const bool presc = P.position_motion.has_value();
     if (presc) {
@@ -765,8 +851,25 @@ void make_rep(const Problem& P, ProblemRep& R) {
         gs.term_count = (int)R.goal_index.size() - gs.term_begin;
         R.goals.push_back(gs);
     }
+    // frame-distance equations: the bodies, and nine terms that belong to no goal
+    size_t nft = 0;
+    for (auto& e : path_eqs) {
+        if (e.kind == MH_PATH_CONTROL_BOUND) continue;
+        if (presc)
+            fail("MocoFrameDistanceConstraint with prescribed kinematics (the coordinates are not NLP states)");
+        const FrameTerms& ft = frame_terms[nft++];
+        e.index = R.cm.index_of_body(ft.body1);
+        e.table = R.cm.index_of_body(ft.body2);
+        e.column = (int)R.goal_index.size();
+        for (int c = 0; c < 9; ++c) {
+            R.goal_index.push_back(0);
+            R.goal_column.push_back(0);
+            R.goal_weight.push_back(ft.terms[c]);
+        }
+    }
     for (auto& e : path_eqs)
-        if (e.table >= 0) e.table = R.cm.index_of_table(bound_tables[e.table].name);
+        if (e.kind == MH_PATH_CONTROL_BOUND && e.table >= 0)
+            e.table = R.cm.index_of_table(bound_tables[e.table].name);
     R.path = path_eqs;
     mh_problem& p = R.problem;
     p = mh_problem{};
@@ -1252,7 +1355,30 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
             pc.lower = read_bound_fn(t);
             pc.upper = read_bound_fn(t);
             pc.equality_with_lower = t.i() != 0;
-            P.path_constraints.push_back(pc);
+            P.add_path_constraint(pc);
+        } else if (rec == "framedist") {
+            FrameDistanceConstraint pc;
+            pc.name = t.s();
+            pc.projection = t.s();
+            const long nv = t.i();
+            for (long k = 0; k < nv; ++k) pc.projection_vector.push_back(t.d());
+            const long n = t.i();
+            for (long k = 0; k < n; ++k) {
+                FrameDistancePair fp;
+                fp.frame1_path = t.s();
+                fp.frame2_path = t.s();
+                fp.minimum_distance = t.d();
+                fp.maximum_distance = t.d();
+                pc.frame_pairs.push_back(fp);
+            }
+            P.add_path_constraint(pc);
+        } else if (rec == "offsetframe") {
+            OffsetFrame f;
+            f.name = t.s();
+            f.body = t.s();
+            t.d3(f.translation);
+            f.path = t.s();
+            M.add_offset_frame(f);
         } else if (rec == "parameter") {
             Parameter par;
             par.name = t.s();

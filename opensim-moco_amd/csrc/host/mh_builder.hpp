@@ -135,6 +135,15 @@ struct Marker {
     std::string path;
 };
 
+// PhysicalOffsetFrame on a body or ground (model.py OffsetFrame): only the
+// translation is kept; path /bodyset/<body>/<name> (/ground/<name>) unless
+// given.
+struct OffsetFrame {
+    std::string name, body;
+    double translation[3] = {0, 0, 0};
+    std::string path;
+};
+
 // A function of time as a piecewise polynomial: breaks[nseg + 1] and
 // coefs[nseg][ncol][degree + 1] in ascending powers of (t - breaks[s]).
 struct Table {
@@ -172,7 +181,12 @@ public:
     std::vector<CoordinateCoupler> constraints;
     std::vector<WrapCylinder> wraps;
     std::vector<SpringGeneralizedForce> springs;
+    std::vector<OffsetFrame> offset_frames;
 
+    void add_offset_frame(OffsetFrame f);
+    // (body name or "ground", location in that body) of the Frame at path:
+    // /ground, /bodyset/<body>, a body name or a registered offset frame
+    bool find_frame(const std::string& path, std::string& body, double location[3]) const;
     void add_body(const Body& b) { bodies.push_back(b); }
     void add_joint(Joint j);
     void add_muscle(Muscle m);
@@ -261,6 +275,19 @@ struct ControlBoundConstraint {
     bool equality_with_lower = false;
 };
 
+// MocoFrameDistanceConstraint (problem.py MocoFrameDistanceConstraint;
+// MocoFrameDistanceConstraint.{h,cpp}); projection_vector empty: not given
+struct FrameDistancePair {
+    std::string frame1_path, frame2_path;
+    double minimum_distance = 0.0, maximum_distance = INFINITY;
+};
+struct FrameDistanceConstraint {
+    std::string name = "frame_distance";
+    std::vector<FrameDistancePair> frame_pairs;
+    std::string projection = "none";
+    std::vector<double> projection_vector;
+};
+
 // MocoParameter (problem.py MocoParameter; MocoParameter.h:91-170):
 // property_element -1 for a scalar property
 struct Parameter {
@@ -277,7 +304,20 @@ struct Problem {
     Bounds time_initial, time_final;
     std::vector<std::pair<std::string, VariableInfo>> state_infos, control_infos;
     std::vector<Goal> goals;
+    // path constraints, by kind, and their declaration order over both kinds
+    // (first: a frame-distance constraint; second: index into its vector);
+    // add them with add_path_constraint
     std::vector<ControlBoundConstraint> path_constraints;
+    std::vector<FrameDistanceConstraint> frame_distance_constraints;
+    std::vector<std::pair<bool, int>> path_order;
+    void add_path_constraint(const ControlBoundConstraint& c) {
+        path_order.emplace_back(false, (int)path_constraints.size());
+        path_constraints.push_back(c);
+    }
+    void add_path_constraint(const FrameDistanceConstraint& c) {
+        path_order.emplace_back(true, (int)frame_distance_constraints.size());
+        frame_distance_constraints.push_back(c);
+    }
     std::optional<Table> position_motion;   // columns: the coordinates' value paths
     Bounds default_speed_bounds{-50.0, 50.0};
     bool bound_activation_from_excitation = true;

@@ -407,51 +407,141 @@ __global__ void __launch_bounds__(256) k_reduce_obj(Layout L, GoalSet GS, int mo
     }
 }
 
-// Pose of body b in ground at coordinates q (the position part of dae_eval's
-// forward pass, dae_device.hpp: parent pose x joint frames x coordinate
-// functions), walking b's ancestors from the ground.
+// One step of the position part of dae_eval's forward pass
+// (dae_device.hpp): the parent's pose in ground (Rp, pp) becomes body B's
+// (parent pose x joint frames x coordinate functions).  q: the coordinates,
+// an array or an accessor (QLane).
+template <class Q>
+__device__ __forceinline__ void joint_pose(const DevModel& M, const Q& q, const mh_body& B, double* Rp,
+        double* pp) {
+    double RGF[9], t0, t1, t2;
+    mm3(Rp, B.R_PF, RGF);
+    mv3(Rp, B.p_PF[0], B.p_PF[1], B.p_PF[2], t0, t1, t2);
+    const double pGF0 = pp[0] + t0, pGF1 = pp[1] + t1, pGF2 = pp[2] + t2;
+    double pFM0 = 0, pFM1 = 0, pFM2 = 0;
+    for (int a = B.axis_begin; a < B.axis_begin + B.axis_count; ++a) {
+        const mh_axis X = M.axes[a];
+        if (X.type != MH_AXIS_TRANSLATION) continue;
+        double v, d1, d2;
+        fn_eval(M, X.func, q, v, d1, d2);
+        pFM0 += v * X.dir[0]; pFM1 += v * X.dir[1]; pFM2 += v * X.dir[2];
+    }
+    mv3(RGF, pFM0, pFM1, pFM2, t0, t1, t2);
+    const double oM0 = pGF0 + t0, oM1 = pGF1 + t1, oM2 = pGF2 + t2;
+    double Rcur[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    for (int a = B.axis_begin; a < B.axis_begin + B.axis_count; ++a) {
+        const mh_axis X = M.axes[a];
+        if (X.type != MH_AXIS_ROTATION) continue;
+        double v, d1, d2;
+        fn_eval(M, X.func, q, v, d1, d2);
+        double Rk[9];
+        axis_rot(X.dir[0], X.dir[1], X.dir[2], v, Rk);
+        mm3(Rcur, Rk, Rcur);
+    }
+    double RGM[9];
+    mm3(RGF, Rcur, RGM);
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            Rp[3 * i + j] = RGM[3 * i] * B.R_BM[3 * j] + RGM[3 * i + 1] * B.R_BM[3 * j + 1] +
+                            RGM[3 * i + 2] * B.R_BM[3 * j + 2];
+    mv3(Rp, B.p_BM[0], B.p_BM[1], B.p_BM[2], t0, t1, t2);
+    pp[0] = oM0 - t0; pp[1] = oM1 - t1; pp[2] = oM2 - t2;
+}
+
+// Pose of body b in ground at coordinates q, walking b's ancestors from the
+// ground.
 __device__ void body_pose(const DevModel& M, const double* q, int b, double* R, double* p) {
     int chain[MH_MARKER_MAX_Q + 1];
     int n = 0;
     for (int x = b; x >= 0 && n <= MH_MARKER_MAX_Q; x = M.bodies[x].parent) chain[n++] = x;
     double Rp[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, pp[3] = {0, 0, 0};
-    for (int ci = n - 1; ci >= 0; --ci) {
-        const mh_body& B = M.bodies[chain[ci]];
-        double RGF[9], t0, t1, t2;
-        mm3(Rp, B.R_PF, RGF);
-        mv3(Rp, B.p_PF[0], B.p_PF[1], B.p_PF[2], t0, t1, t2);
-        const double pGF0 = pp[0] + t0, pGF1 = pp[1] + t1, pGF2 = pp[2] + t2;
-        double pFM0 = 0, pFM1 = 0, pFM2 = 0;
-        for (int a = B.axis_begin; a < B.axis_begin + B.axis_count; ++a) {
-            const mh_axis X = M.axes[a];
-            if (X.type != MH_AXIS_TRANSLATION) continue;
-            double v, d1, d2;
-            fn_eval(M, X.func, q, v, d1, d2);
-            pFM0 += v * X.dir[0]; pFM1 += v * X.dir[1]; pFM2 += v * X.dir[2];
-        }
-        mv3(RGF, pFM0, pFM1, pFM2, t0, t1, t2);
-        const double oM0 = pGF0 + t0, oM1 = pGF1 + t1, oM2 = pGF2 + t2;
-        double Rcur[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
-        for (int a = B.axis_begin; a < B.axis_begin + B.axis_count; ++a) {
-            const mh_axis X = M.axes[a];
-            if (X.type != MH_AXIS_ROTATION) continue;
-            double v, d1, d2;
-            fn_eval(M, X.func, q, v, d1, d2);
-            double Rk[9];
-            axis_rot(X.dir[0], X.dir[1], X.dir[2], v, Rk);
-            mm3(Rcur, Rk, Rcur);
-        }
-        double RGM[9];
-        mm3(RGF, Rcur, RGM);
-        for (int i = 0; i < 3; ++i)
-            for (int j = 0; j < 3; ++j)
-                Rp[3 * i + j] = RGM[3 * i] * B.R_BM[3 * j] + RGM[3 * i + 1] * B.R_BM[3 * j + 1] +
-                                RGM[3 * i + 2] * B.R_BM[3 * j + 2];
-        mv3(Rp, B.p_BM[0], B.p_BM[1], B.p_BM[2], t0, t1, t2);
-        pp[0] = oM0 - t0; pp[1] = oM1 - t1; pp[2] = oM2 - t2;
-    }
+    for (int ci = n - 1; ci >= 0; --ci) joint_pose(M, q, M.bodies[chain[ci]], Rp, pp);
     for (int i = 0; i < 9; ++i) R[i] = Rp[i];
     for (int i = 0; i < 3; ++i) p[i] = pp[i];
+}
+
+// The coordinates of one point with a lane's perturbation applied on the fly
+// (coordinate s moved by d; s = -1: none): nothing is staged per thread.
+struct QLane {
+    const double* __restrict__ q;
+    int s;
+    double d;
+    __device__ __forceinline__ double operator[](int j) const {
+#pragma clang fp contract(off)
+        return j == s ? q[j] + d : q[j];
+    }
+};
+
+// MocoFrameDistanceConstraint::calcPathConstraintErrorsImpl
+// (MocoFrameDistanceConstraint.cpp:114-136) from the two bodies' poses
+// (12 doubles: R then p; null: ground) and the equation's nine terms, in
+// the order the header states, each product and sum rounded on its own.
+__device__ __forceinline__ double frame_distance_error(int kind, const double* A, const double* B,
+        const double* __restrict__ w) {
+#pragma clang fp contract(off)
+    double a0 = w[0], a1 = w[1], a2 = w[2], b0 = w[3], b1 = w[4], b2 = w[5];
+    if (A) {
+        a0 = A[9] + (A[0] * w[0] + A[1] * w[1] + A[2] * w[2]);
+        a1 = A[10] + (A[3] * w[0] + A[4] * w[1] + A[5] * w[2]);
+        a2 = A[11] + (A[6] * w[0] + A[7] * w[1] + A[8] * w[2]);
+    }
+    if (B) {
+        b0 = B[9] + (B[0] * w[3] + B[1] * w[4] + B[2] * w[5]);
+        b1 = B[10] + (B[3] * w[3] + B[4] * w[4] + B[5] * w[5]);
+        b2 = B[11] + (B[6] * w[3] + B[7] * w[4] + B[8] * w[5]);
+    }
+    const double r0 = b0 - a0, r1 = b1 - a1, r2 = b2 - a2;
+    double e0 = r0, e1 = r1, e2 = r2;
+    if (kind != MH_PATH_FRAME_DISTANCE) {
+        const double n0 = w[6], n1 = w[7], n2 = w[8];
+        const double d = r0 * n0 + r1 * n1 + r2 * n2;
+        if (kind == MH_PATH_FRAME_DISTANCE_VECTOR) { e0 = d * n0; e1 = d * n1; e2 = d * n2; }
+        else { e0 = r0 - d * n0; e1 = r1 - d * n1; e2 = r2 - d * n2; }
+    }
+    return e0 * e0 + e1 * e1 + e2 * e2;
+}
+
+// The frame-distance equations of every point and lane (FrameDist, core.hpp):
+// block = point; first the ground pose of each distinct body per lane into
+// LDS (once per lane, not per equation), then every equation's error.
+// Point pt's coordinates are q0[pt * qstride ..]; lanes 0..nl-1 are written
+// to out[(pt * ostride + lane) * npc + e].  The constraint rows run it over
+// the shard's mesh points (nl = 1: eval_g), mh_eval_path and the sparsity
+// detection over probe rows (nl = 1, ostride = 1): the same code, so a
+// quotient of probe values reproduces a Jacobian entry bit for bit.
+__global__ void __launch_bounds__(128) k_frame_distance(DevModel M, PathEqs P, int fd, double h, int nl,
+        const double* __restrict__ q0, long qstride, int ostride, double* __restrict__ out) {
+    extern __shared__ double fd_pose[];   // [lane][slot][12]
+    const FrameDist& F = P.F;
+    const int npc = P.npc, ns = F.nslots;
+    const int pt = blockIdx.x;
+    const double* q = q0 + (long)pt * qstride;
+    for (int w = threadIdx.x; w < nl * ns; w += blockDim.x) {
+        const int ln = w / ns, sl = w - ln * ns;
+        QLane Q{q, -1, 0.0};
+        if (ln > 0) {
+            const int l = ln - 1;
+            Q.s = F.coord(npc)[l < F.nlc ? l : l - F.nlc];
+            Q.d = fd == MH_FD_BACKWARD || l >= F.nlc ? -h : h;
+        }
+        const int cb = F.chain(npc)[2 * sl], cn = F.chain(npc)[2 * sl + 1];
+        const int* bodies = F.bodies(npc) + cb;
+        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
+        for (int ci = 0; ci < cn; ++ci) joint_pose(M, Q, M.bodies[bodies[ci]], R, p);
+        double* o = fd_pose + (long)w * 12;
+        for (int i = 0; i < 9; ++i) o[i] = R[i];
+        for (int i = 0; i < 3; ++i) o[9 + i] = p[i];
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < nl * npc; w += blockDim.x) {
+        const int ln = w / npc, e = w - ln * npc;
+        const mh_path_equation E = P.eq[e];
+        if (E.kind == MH_PATH_CONTROL_BOUND) continue;
+        const int s1 = F.slot(npc)[2 * e], s2 = F.slot(npc)[2 * e + 1];
+        const double* A = s1 < 0 ? nullptr : fd_pose + ((long)ln * ns + s1) * 12;
+        const double* B = s2 < 0 ? nullptr : fd_pose + ((long)ln * ns + s2) * 12;
+        out[((long)pt * ostride + ln) * npc + e] = frame_distance_error(E.kind, A, B, F.terms + E.column);
+    }
 }
 
 // MocoMarkerFinalGoal (MocoMarkerFinalGoal.cpp:29-34): |p_G(q(tf)) - r|^2
@@ -1370,6 +1460,22 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
     c->pc.assign(p->path, p->path + p->npath);
     for (int e = 0; e < c->npc; ++e) {
         const mh_path_equation& E = c->pc[e];
+        if (E.kind >= MH_PATH_FRAME_DISTANCE && E.kind <= MH_PATH_FRAME_DISTANCE_PLANE) {
+            c->has_fdist = true;
+            if (E.index < -1 || E.index >= M.nbodies || E.table < -1 || E.table >= M.nbodies)
+                return set_err(MH_ERR_INVALID, "path equation %d: frame body out of range", e);
+            if (E.column < 0 || (int64_t)E.column + 9 > p->nterms || !p->goal_weight)
+                return set_err(MH_ERR_INVALID, "path equation %d: term range out of range", e);
+            if (!(E.g.lower >= 0.0) || !(E.g.upper >= E.g.lower))
+                return set_err(MH_ERR_INVALID, "path equation %d: negative or inverted distance bounds", e);
+            if (c->presc || M.nq > MH_MARKER_MAX_Q)
+                return set_err(MH_ERR_UNSUPPORTED, "path equation %d: frame distance needs coordinate states "
+                               "(<= %d; no prescribed kinematics)", e, MH_MARKER_MAX_Q);
+            const double* n = p->goal_weight + E.column + 6;
+            if (E.kind != MH_PATH_FRAME_DISTANCE && n[0] == 0.0 && n[1] == 0.0 && n[2] == 0.0)
+                return set_err(MH_ERR_INVALID, "path equation %d: zero projection vector", e);
+            continue;
+        }
         if (E.kind != MH_PATH_CONTROL_BOUND)
             return set_err(MH_ERR_UNSUPPORTED, "path equation %d: kind %d", e, E.kind);
         if (E.index < 0 || E.index >= c->NC || E.table < -1 || E.table >= M.ntables ||
@@ -1644,6 +1750,51 @@ static int build_seeds(mh_ctx* c);
 static const TaskInfo* backend_tasks(const Backend* b);
 static bool interval_fits(const mh_ctx* c, int mode);
 
+// FrameDist's int table (core.hpp) and counts for the frame-distance
+// equations of c->pc: one slot per distinct body, its ancestor chain root
+// first, and a lane for every coordinate that drives a body of some chain.
+static FrameDist frame_distance_tables(mh_ctx* c, const mh_model& M, const std::vector<int>& coord_body) {
+    FrameDist F{};
+    if (!c->has_fdist) return F;
+    std::vector<int> slot(2 * (size_t)c->npc, -1), slot_body, chain, bodies;
+    auto slot_of = [&](int b) {
+        if (b < 0) return -1;
+        for (size_t i = 0; i < slot_body.size(); ++i)
+            if (slot_body[i] == b) return (int)i;
+        slot_body.push_back(b);
+        return (int)slot_body.size() - 1;
+    };
+    for (int e = 0; e < c->npc; ++e) {
+        if (c->pc[e].kind == MH_PATH_CONTROL_BOUND) continue;
+        slot[2 * e] = slot_of(c->pc[e].index);
+        slot[2 * e + 1] = slot_of(c->pc[e].table);
+    }
+    std::vector<char> on_chain(M.nbodies, 0);
+    for (int b : slot_body) {
+        std::vector<int> up;
+        for (int x = b; x >= 0; x = M.bodies[x].parent) { up.push_back(x); on_chain[x] = 1; }
+        chain.push_back((int)bodies.size());
+        chain.push_back((int)up.size());
+        bodies.insert(bodies.end(), up.rbegin(), up.rend());
+    }
+    std::vector<int> lane(M.nq, -1), coord;
+    for (int j = 0; j < M.nq; ++j)
+        if (on_chain[coord_body[j]]) { lane[j] = (int)coord.size(); coord.push_back(j); }
+    F.nslots = (int)slot_body.size();
+    F.nlc = (int)coord.size();
+    F.nl = 1 + (c->fd == MH_FD_CENTRAL ? 2 : 1) * F.nlc;
+    F.nq = M.nq;
+    F.k0 = c->k0;
+    F.kshift = c->scheme == MH_HERMITE_SIMPSON ? 1 : 0;
+    c->fd_tab = slot;
+    c->fd_tab.insert(c->fd_tab.end(), chain.begin(), chain.end());
+    c->fd_tab.insert(c->fd_tab.end(), lane.begin(), lane.end());
+    c->fd_tab.insert(c->fd_tab.end(), coord.begin(), coord.end());
+    c->fd_tab.insert(c->fd_tab.end(), bodies.begin(), bodies.end());
+    c->fd_lds = sizeof(double) * 12 * (size_t)F.nl * std::max(1, F.nslots);
+    return F;
+}
+
 extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out) {
     if (!p || !o || !out) return set_err(MH_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -1691,7 +1842,11 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
         d[5] = std::exp(4.0) - d[4];
     }
 
+    FrameDist FD = frame_distance_tables(c.get(), M, coord_body);
+    if (c->fd_lds > 64 * 1024)
+        return set_err(MH_ERR_UNSUPPORTED, "frame distance: %d bodies x %d lanes exceed the LDS", FD.nslots, FD.nl);
     Arena A;
+    const size_t o_fdtab = A.put(c->fd_tab.data(), c->fd_tab.size());
     const size_t o_bodies = A.put(M.bodies, M.nbodies), o_axes = A.put(M.axes, M.naxes),
                  o_funcs = A.put(M.functions, M.nfunctions), o_kx = A.put(M.knot_x, M.nknots),
                  o_ky = A.put(M.knot_y, M.nknots), o_kb = A.put(kb.data(), kb.size()),
@@ -1796,6 +1951,8 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     }
     const size_t o_Y = A.reserve(sizeof(double) * (size_t)c->nk * std::max(1, c->NO) * stride);
     const size_t o_Yg = A.reserve(sizeof(double) * (size_t)c->nk * std::max(1, c->NO));
+    // frame-distance values of the shard's mesh points (ib..ie) at all lanes
+    const size_t o_pf = c->has_fdist ? A.reserve(sizeof(double) * (size_t)(nint + 1) * FD.nl * c->npc) : 0;
     const size_t o_g = A.reserve(sizeof(double) * ((size_t)c->nep + (size_t)nint * c->rpi + c->ntail));
     const size_t o_vals = A.reserve(sizeof(double) * ((size_t)c->nnz_ep + (size_t)nint * c->nnz_int + c->nnz_tail));
     const size_t o_C = A.reserve(sizeof(double) * (size_t)c->G * std::max(1, c->ngoals));
@@ -1985,7 +2142,12 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     c->d_ctgen = (int*)(b + o_ctgen);
     c->d_rl_e = (int*)(b + o_rl_e);
     c->d_rl_w = (uint32_t*)(b + o_rl_w);
-    c->P = PathEqs{c->npc, (const mh_path_equation*)(b + o_pc), D.tabs, D.brk, D.coef, c->d_grid};
+    if (c->has_fdist) {
+        FD.terms = c->GS.gw;
+        FD.pf = (double*)(b + o_pf);
+        FD.tab = (const int*)(b + o_fdtab);
+    }
+    c->P = PathEqs{c->npc, (const mh_path_equation*)(b + o_pc), D.tabs, D.brk, D.coef, c->d_grid, FD};
     c->E = EndpointEqs{c->nep, c->nnz_ep, 1 + c->NI, (const mh_endpoint_equation*)(b + o_ep),
                        (const TplEntry*)(b + o_eptpl)};
 
@@ -2337,6 +2499,14 @@ static int launch_stage(mh_ctx* c, int stage, int kind, const double* x, double*
     if (stage == 0) {
         apply_params(c, x);   // MocoParameters: the model copies for this iterate
         (glane ? c->be_lane : c->be)->eval(c, x, kind == 0 ? 0 : 1, kind == 0 ? c->d_Yg : c->d_Y);
+        if (c->has_fdist) {
+            // the frame-distance rows' values (and lanes) at the shard's mesh points
+            const FrameDist& F = c->P.F;
+            const int nl = kind == 0 ? 1 : F.nl;
+            hipLaunchKernelGGL(k_frame_distance, dim3((unsigned)(c->ie - c->ib + 1)), dim3(128),
+                    sizeof(double) * 12 * nl * F.nslots, c->stream, c->M, c->P, c->fd, c->h, nl,
+                    x + 2 + (long)c->k0 * c->NS, (long)c->NS << F.kshift, F.nl, F.pf);
+        }
         HIPCHK(hipGetLastError());
         return MH_OK;
     }
@@ -2872,6 +3042,9 @@ extern "C" int mh_batch_create(mh_ctx* const* ctxs, int32_t count, mh_batch** ou
     for (int b = 0; b < count; ++b) {
         const mh_ctx* c = ctxs[b];
         if (!c) return set_err(MH_ERR_INVALID, "null context %d", b);
+        if (c->has_fdist)
+            return set_err(MH_ERR_UNSUPPORTED, "context %d: batches do not evaluate frame-distance path "
+                           "constraints", b);
         if (!c->be->batch || !c->use_interval[0] || !c->use_interval[1] || c->jac_seeds || c->use_roles)
             return set_err(MH_ERR_UNSUPPORTED, "context %d: batches need the task back end with the fused "
                            "interval kernel (no global seeds, no k_role)", b);
@@ -3103,7 +3276,42 @@ __global__ void __launch_bounds__(256) k_path_probe(PathEqs P, int np, int NS, i
     if (w >= np * P.npc) return;
     const int q = w / P.npc, e = w - q * P.npc;
     const double* r = in + (long)q * W;
-    out[w] = path_value(P, e, r[0], r[1 + NS + P.eq[e].index]);
+    const mh_path_equation E = P.eq[e];
+    if (E.kind != MH_PATH_CONTROL_BOUND) return;   // k_frame_distance wrote it
+    out[w] = path_value(P, e, r[0], r[1 + NS + E.index]);
+}
+
+// The path equations of np probe rows on the device (din -> dout[np][npc]):
+// frame-distance equations by k_frame_distance over the rows' coordinates,
+// the others by k_path_probe.
+static int path_probe(mh_ctx* c, int np, const double* din, double* dout) {
+    const int W = 1 + c->NI;
+    if (c->has_fdist)
+        hipLaunchKernelGGL(k_frame_distance, dim3((unsigned)np), dim3(128), sizeof(double) * 12 * c->P.F.nslots,
+                c->stream, c->M, c->P, c->fd, c->h, 1, din + 1, (long)W, 1, dout);
+    const int nthr = np * c->npc;
+    k_path_probe<<<(nthr + 255) / 256, 256, 0, c->stream>>>(c->P, np, c->NS, W, din, dout);
+    HIPCHK(hipGetLastError());
+    return MH_OK;
+}
+
+extern "C" int mh_eval_path(mh_ctx* c, int32_t np, const double* inputs, double* outputs) {
+    if (!c || !inputs || !outputs || np < 0) return set_err(MH_ERR_INVALID, "bad argument");
+    if (np == 0 || c->npc == 0) return MH_OK;
+    HIPCHK(hipSetDevice(c->device));
+    double *din = nullptr, *dout = nullptr;
+    const size_t nin = (size_t)np * (1 + c->NI), nout = (size_t)np * c->npc;
+    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
+    HIPCHK(hipMalloc(&dout, sizeof(double) * nout));
+    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
+    const int rc = path_probe(c, np, din, dout);
+    if (!rc) {
+        HIPCHK(hipMemcpyAsync(outputs, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    }
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    return rc;
 }
 
 // Endpoint-equation values of np probe rows [initial_time, initial inputs,
@@ -3207,9 +3415,8 @@ static int detect_sparsity(mh_ctx* c, const mh_options* o) {
         HIPCHK(hipMalloc(&din, sizeof(double) * in.size()));
         HIPCHK(hipMalloc(&dout, sizeof(double) * pout.size()));
         HIPCHK(hipMemcpyAsync(din, in.data(), sizeof(double) * in.size(), hipMemcpyHostToDevice, c->stream));
-        const int nthr = rows * NPC;
-        k_path_probe<<<(nthr + 255) / 256, 256, 0, c->stream>>>(c->P, rows, c->NS, W, din, dout);
-        HIPCHK(hipGetLastError());
+        const int rc = path_probe(c, rows, din, dout);
+        if (rc) return rc;
         HIPCHK(hipMemcpyAsync(pout.data(), dout, sizeof(double) * pout.size(), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
         (void)hipFree(din);

@@ -155,6 +155,7 @@ class mh_goal(C.Structure):
 
 MH_ABI_VERSION = 8     # include/mocohip.h
 MH_PATH_CONTROL_BOUND = 0
+MH_PATH_FRAME_DISTANCE, MH_PATH_FRAME_DISTANCE_VECTOR, MH_PATH_FRAME_DISTANCE_PLANE = 1, 2, 3
 MH_ENDPOINT_INITIAL_ACTIVATION = 0
 
 
@@ -243,6 +244,7 @@ MOCOHIP_SYMBOLS = {
     "mh_tnlp_eval_g_device": (i32, [C.c_void_p, C.c_void_p, i32, C.c_void_p]),
     "mh_tnlp_eval_jac_g_device": (i32, [C.c_void_p, C.c_void_p, i32, C.c_void_p]),
     "mh_eval_dae": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
+    "mh_eval_path": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
     "mh_set_timing": (i32, [C.c_void_p, i32]),
     "mh_get_backend_flags": (i32, [C.c_void_p, C.c_char_p, i32]),
     "mh_last_timings": (i32, [C.c_void_p, P(f64)]),

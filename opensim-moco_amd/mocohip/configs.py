@@ -26,7 +26,8 @@ from .model import (Body, Coordinate, CoordinateActuator, DataTable,
 from . import abi
 from .osim import add_reserves
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm,
-                      MocoControlBoundConstraint, MocoControlGoal, MocoInitialActivationGoal,
+                      MocoControlBoundConstraint, MocoControlGoal, MocoFrameDistanceConstraint,
+                      MocoInitialActivationGoal,
                       MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoProblem, MocoStateTrackingGoal,
                       PiecewiseLinearFunction)
 from .solver import MocoHipSolver, MocoStudy
@@ -351,6 +352,63 @@ def gait10dof18musc(num_mesh_intervals: int = 200, muscles: bool = True,
         r.set_upper_bound(Constant(0.5))
     s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals,
                       optim_finite_difference_scheme=fd_scheme, multibody_dynamics_mode=dynamics)
+    return MocoStudy(p, s)
+
+
+def gait10dof18musc_feet_apart(num_mesh_intervals: int = 200, projection: str = "none",
+                               **kw) -> MocoStudy:
+    """The gait10dof18musc study plus a MocoFrameDistanceConstraint that keeps
+    the feet apart: one pair of offset frames on calcn_r and calcn_l, at least
+    0.1 m apart ("vector" / "plane": along / normal to the medio-lateral
+    direction, slightly tilted so that no component of it is zero)."""
+    st = gait10dof18musc(num_mesh_intervals, **kw)
+    m = st.problem.model
+    m.add_offset_frame("mid_foot_r", "calcn_r", (0.1, 0.02, 0.01))
+    m.add_offset_frame("mid_foot_l", "calcn_l", (0.1, 0.02, -0.01))
+    c = st.problem.add_path_constraint(MocoFrameDistanceConstraint("feet_apart"))
+    c.add_frame_pair("/bodyset/calcn_r/mid_foot_r", "/bodyset/calcn_l/mid_foot_l", 0.1, math.inf)
+    c.set_projection(projection)
+    if projection != "none":
+        c.set_projection_vector((0.1, 0.2, 1.0))
+    return st
+
+
+def gimbal_frame_distance(num_mesh_intervals: int = 25, dynamics: str = "explicit",
+                          scheme: str = "hermite-simpson", fd_scheme: str = "forward") -> MocoStudy:
+    """testConstraints.cpp:1591-1658 (MocoFrameDistanceConstraint): a body of
+    mass 1, inertia 1 on a GimbalJoint at (0, 1, 0) of ground (parent
+    orientation (0, 0, -pi/2), child location (-1, 0, 0)), reserves of optimal
+    force 50 on qx, qy, qz (ModOpAddReserves(50)), time [0, 0.5], the state
+    infos of :1626-1632, the pair /ground - /bodyset/body at least 0.1 apart,
+    and a MocoMarkerFinalGoal of the body origin to (0, 0.292893, 0.707107).
+    At q = 0 the body origin is the ground origin, so the straight path of qy
+    from pi/4 to -pi/4 violates the constraint -- and there the constraint's
+    gradient vanishes.  fd_scheme: forward differences by default, a deviation
+    from the reference's solver default (central): from the bounds guess the
+    interior-point restatement (mocohip.ipm) ends in Restoration_Failed with
+    central differences (frame-distance constraints)."""
+    m = Model("gimbal_pendulum")
+    m.add_body(Body("body", 1.0, (0, 0, 0), (1, 1, 1, 0, 0, 0)))
+    qx, qy, qz = (Coordinate(n, (-math.inf, math.inf)) for n in ("qx", "qy", "qz"))
+    m.add_joint(Joint.gimbal("gimbal", "ground", "body", qx, qy, qz, loc_in_parent=(0, 1, 0),
+                             orient_in_parent=(0, 0, -math.pi / 2), loc_in_child=(-1, 0, 0)))
+    m.add_marker(Marker("marker", "body", (0.0, 0.0, 0.0)))
+    m.add_offset_frame("body_center", "body", (-0.5, 0.0, 0.0))
+    add_reserves(m, 50.0)
+    p = MocoProblem(m)
+    p.set_time_bounds(0, 0.5)
+    third = math.pi / 3
+    p.set_state_info("/jointset/gimbal/qx/value", (-third, third), 0)
+    p.set_state_info("/jointset/gimbal/qy/value", (-third, third), math.pi / 4, -math.pi / 4)
+    p.set_state_info("/jointset/gimbal/qz/value", (-third, third), 0)
+    for n in ("qx", "qy", "qz"):
+        p.set_state_info(f"/jointset/gimbal/{n}/speed", (-10, 10), 0, 0)
+    c = p.add_path_constraint(MocoFrameDistanceConstraint())
+    c.add_frame_pair("/ground", "/bodyset/body", 0.1, math.inf)
+    p.add_goal(MocoMarkerFinalGoal("final_marker", point_name="/markerset/marker",
+                                   reference_location=(0.0, 0.292893, 0.707107)))
+    s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals, transcription_scheme=scheme,
+                      multibody_dynamics_mode=dynamics, optim_finite_difference_scheme=fd_scheme)
     return MocoStudy(p, s)
 
 

@@ -15,7 +15,8 @@ import numpy as np
 
 from .model import CoordinateActuator, DataTable, DeGrooteFregly2016Muscle
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm, MocoControlBoundConstraint,
-                      MocoControlGoal, MocoFinalTimeGoal, MocoInitialActivationGoal, MocoMarkerFinalGoal,
+                      MocoControlGoal, MocoFinalTimeGoal, MocoFrameDistanceConstraint, MocoInitialActivationGoal,
+                      MocoMarkerFinalGoal,
                       MocoStateTrackingGoal, MocoSumSquaredStateGoal, PiecewiseLinearFunction)
 from .splines import gcv_interpolating_ppoly
 
@@ -122,6 +123,8 @@ def describe(study) -> str:
                              _d(f.viscosity), _s(f.path)]))
     for mk in m.markers.values():
         out.append(f"marker {_s(mk.name)} {_s(mk.body)} {_ds(mk.location)} {_s(mk.path)}")
+    for fr in m.offset_frames.values():
+        out.append(f"offsetframe {_s(fr.name)} {_s(fr.body)} {_ds(fr.translation)} {_s(fr.path)}")
     for k in m.constraints:
         out.append(f"constraint {_s(k.name)} {_s(k.dependent)} {_fn(k.function)} {_d(k.scale_factor)}")
     for name, t in m.tables.items():
@@ -162,6 +165,13 @@ def describe(study) -> str:
         else:
             raise TypeError(f"unsupported goal {type(g).__name__}")
     for pc in p.path_constraints:
+        if isinstance(pc, MocoFrameDistanceConstraint):
+            vec = [] if pc.projection_vector is None else list(pc.projection_vector)
+            out.append(" ".join(["framedist", _s(pc.name), _s(pc.projection), str(len(vec))]
+                                + [_d(v) for v in vec] + [str(len(pc.frame_pairs))]
+                                + [f"{_s(fp.frame1_path)} {_s(fp.frame2_path)} {_d(fp.minimum_distance)} "
+                                   f"{_d(fp.maximum_distance)}" for fp in pc.frame_pairs]))
+            continue
         if not isinstance(pc, MocoControlBoundConstraint):
             raise TypeError(f"unsupported path constraint {type(pc).__name__}")
         out.append(" ".join(["pathcon", _s(pc.name), str(len(pc.control_paths))]

@@ -164,6 +164,17 @@ class Joint:
         ], **frames)
 
     @staticmethod
+    def gimbal(name, parent, child, qx: Coordinate, qy: Coordinate, qz: Coordinate,
+               **frames) -> "Joint":
+        """GimbalJoint: rotations about x, y, z of the joint frame in
+        body-fixed order."""
+        return Joint(name, parent, child, [qx, qy, qz], [
+            Axis(abi.MH_AXIS_ROTATION, (1, 0, 0), Function.linear(qx.name)),
+            Axis(abi.MH_AXIS_ROTATION, (0, 1, 0), Function.linear(qy.name)),
+            Axis(abi.MH_AXIS_ROTATION, (0, 0, 1), Function.linear(qz.name)),
+        ], **frames)
+
+    @staticmethod
     def weld(name, parent, child, **frames) -> "Joint":
         return Joint(name, parent, child, [], [], **frames)
 
@@ -278,6 +289,17 @@ class Marker:
 
 
 @dataclass
+class OffsetFrame:
+    """OpenSim::PhysicalOffsetFrame on a body (or ground); path
+    /bodyset/<body>/<name> (/ground/<name>).  Only the translation is kept:
+    it is all the frame's position in ground needs."""
+    name: str
+    body: str                # body name or "ground"
+    translation: Sequence[float] = (0.0, 0.0, 0.0)
+    path: str = ""
+
+
+@dataclass
 class DataTable:
     """Time series; splined with the GCVSpline restatement (splines.py)."""
     name: str
@@ -325,6 +347,7 @@ class Model:
         self.constraints: List[CoordinateCouplerConstraint] = []   # enabled ones
         self.wraps: Dict[str, WrapCylinder] = {}
         self.springs: List[SpringGeneralizedForce] = []
+        self.offset_frames: Dict[str, OffsetFrame] = {}   # by path
 
     # building ---------------------------------------------------------------
     def add_body(self, body: Body):
@@ -402,6 +425,28 @@ class Model:
             mk.path = f"/markerset/{mk.name}"
         self.markers[mk.path] = mk
         return mk
+
+    def add_offset_frame(self, name: str, body: str, translation=(0.0, 0.0, 0.0)) -> OffsetFrame:
+        if body != "ground" and body not in self.bodies:
+            raise ValueError(f"offset frame '{name}': no body '{body}'")
+        path = f"/ground/{name}" if body == "ground" else f"/bodyset/{body}/{name}"
+        fr = OffsetFrame(name, body, tuple(float(v) for v in translation), path)
+        self.offset_frames[path] = fr
+        return fr
+
+    def find_frame(self, path: str):
+        """(body name or "ground", location in that body) of the Frame at
+        ``path``: /ground, /bodyset/<body>, a body name, or a registered
+        offset frame (by path or name); None when there is none."""
+        if path in ("/ground", "ground"):
+            return "ground", (0.0, 0.0, 0.0)
+        for b in self.bodies:
+            if path in (b, "/bodyset/" + b):
+                return b, (0.0, 0.0, 0.0)
+        for fr in self.offset_frames.values():
+            if path in (fr.path, fr.name):
+                return fr.body, tuple(fr.translation)
+        return None
 
     # ordering ---------------------------------------------------------------
     def tree_order(self) -> List[Joint]:
@@ -763,6 +808,8 @@ def model_to_dict(m: Model) -> dict:
         "springs": [{"name": f.name, "coordinate": f.coordinate, "stiffness": f.stiffness,
                      "rest_length": f.rest_length, "viscosity": f.viscosity, "path": f.path}
                     for f in m.springs],
+        **({"offset_frames": [{"name": f.name, "body": f.body, "translation": list(f.translation)}
+                              for f in m.offset_frames.values()]} if m.offset_frames else {}),
     }
 
 
@@ -801,4 +848,6 @@ def model_from_dict(d: dict) -> Model:
     for f in d.get("springs", []):
         m.add_spring(SpringGeneralizedForce(f["name"], f["coordinate"], f["stiffness"], f["rest_length"],
                                             f["viscosity"], f.get("path", "")))
+    for f in d.get("offset_frames", []):
+        m.add_offset_frame(f["name"], f["body"], tuple(f["translation"]))
     return m

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import abi
 from .model import CompiledModel, CoordinateActuator, DataTable, \
-    DeGrooteFregly2016Muscle, Model, SpringGeneralizedForce
+    DeGrooteFregly2016Muscle, Model, SpringGeneralizedForce, unit3
 from .splines import gcv_interpolating_ppoly
 
 NAN = float("nan")
@@ -173,6 +173,42 @@ class MocoControlBoundConstraint:
 
 
 @dataclass
+class MocoFrameDistanceConstraintPair:
+    """MocoFrameDistanceConstraintPair (MocoFrameDistanceConstraint.h): the
+    distance between the origins of two model frames stays within
+    [minimum_distance, maximum_distance]."""
+    frame1_path: str = ""
+    frame2_path: str = ""
+    minimum_distance: float = 0.0
+    maximum_distance: float = math.inf
+
+
+@dataclass
+class MocoFrameDistanceConstraint:
+    """MocoFrameDistanceConstraint (Moco/Moco/MocoFrameDistanceConstraint.
+    {h,cpp}): per frame pair one path-constraint equation, the squared
+    distance between the two frame origins in ground -- or of its projection
+    onto ``projection_vector`` ("vector") or onto the plane normal to it
+    ("plane") -- bounded by [minimum^2, maximum^2] at every mesh point."""
+    name: str = "frame_distance"
+    frame_pairs: List[MocoFrameDistanceConstraintPair] = field(default_factory=list)
+    projection: str = "none"
+    projection_vector: Optional[Sequence[float]] = None
+
+    def add_frame_pair(self, pair, frame2_path=None, minimum_distance=0.0, maximum_distance=math.inf):
+        if not isinstance(pair, MocoFrameDistanceConstraintPair):
+            pair = MocoFrameDistanceConstraintPair(pair, frame2_path, minimum_distance, maximum_distance)
+        self.frame_pairs.append(pair)
+        return pair
+
+    def set_projection(self, projection: str):
+        self.projection = projection
+
+    def set_projection_vector(self, v):
+        self.projection_vector = tuple(float(a) for a in v)
+
+
+@dataclass
 class ImplicitAuxiliaryDerivativesTerm:
     """MocoDirectCollocationSolver minimize_implicit_auxiliary_derivatives /
     implicit_auxiliary_derivatives_weight as an objective term
@@ -284,7 +320,7 @@ class ProblemRep:
     def __init__(self, problem: MocoProblem):
         self.problem = problem
         model = problem.model
-        path_eqs, bound_tables = self._path_equations(problem)
+        path_eqs, bound_tables, frame_terms = self._path_equations(problem)
         kin = problem.position_motion
         extra = list(bound_tables)
         if kin is not None:
@@ -423,6 +459,18 @@ class ProblemRep:
             goals.append(gs)
             goal_names.append(getattr(g, "name", "") or type(g).__name__)
 
+        # frame-distance equations: the bodies, and nine terms that belong to
+        # no goal (include/mocohip.h mh_path_kind)
+        for e, (b1, b2, vals) in zip([q for q in path_eqs if q.kind != abi.MH_PATH_CONTROL_BOUND],
+                                     frame_terms):
+            if kin is not None:
+                raise NotImplementedError("MocoFrameDistanceConstraint with prescribed kinematics "
+                                          "(the coordinates are not NLP states)")
+            e.index, e.table = self.compiled.body_index[b1], self.compiled.body_index[b2]
+            e.column = len(gidx)
+            for v in vals:
+                gidx.append(0); gcol.append(0); gw.append(float(v))
+
         self._sinfo = (abi.mh_variable_info * max(1, len(self.state_infos)))(
             *[_vi(i) for i in self.state_infos])
         self._cinfo = (abi.mh_variable_info * max(1, len(self.control_infos)))(
@@ -445,7 +493,7 @@ class ProblemRep:
         p.goal_column = abi.iptr(self._gcol)
         p.goal_weight = abi.dptr(self._gw)
         for e in path_eqs:
-            if e.table >= 0:   # bound table index: after the model's own
+            if e.kind == abi.MH_PATH_CONTROL_BOUND and e.table >= 0:   # bound table index: after the model's own
                 e.table = self.compiled.table_index[bound_tables[e.table].name]
         self._path = (abi.mh_path_equation * max(1, len(path_eqs)))(*path_eqs)
         p.prescribed_kinematics = 0
@@ -580,7 +628,11 @@ class ProblemRep:
         cidx = {n: i for i, n in enumerate(names)}
         eqs: List[abi.mh_path_equation] = []
         tables: List[DataTable] = []
+        frame_terms: List[tuple] = []   # per frame-distance equation: body 1, body 2, nine doubles
         for ci, pc in enumerate(problem.path_constraints):
+            if isinstance(pc, MocoFrameDistanceConstraint):
+                ProblemRep._frame_distance_equations(problem.model, pc, eqs, frame_terms)
+                continue
             if not isinstance(pc, MocoControlBoundConstraint):
                 raise TypeError(f"unsupported path constraint {type(pc).__name__}")
             has_lo, has_up = pc.lower_bound is not None, pc.upper_bound is not None
@@ -635,4 +687,49 @@ class ProblemRep:
                     else:
                         e.g.lower, e.g.upper = -math.inf, 0.0
                     eqs.append(e)
-        return eqs, tables
+        return eqs, tables, frame_terms
+
+    @staticmethod
+    def _frame_distance_equations(model: Model, pc: "MocoFrameDistanceConstraint", eqs, frame_terms):
+        """MocoFrameDistanceConstraint::initializeOnModelImpl
+        (MocoFrameDistanceConstraint.cpp:56-112): its checks and messages,
+        bounds [minimum^2, maximum^2], one equation per pair."""
+        pairs = []
+        for pair in pc.frame_pairs:
+            frames = []
+            for path in (pair.frame1_path, pair.frame2_path):
+                fr = model.find_frame(path)
+                if fr is None:
+                    raise ValueError(f"Could not find frame '{path}'.")
+                frames.append(fr)
+            lo, hi = float(pair.minimum_distance), float(pair.maximum_distance)
+            if lo < 0:
+                raise ValueError("Expected the minimum distance for this frame pair to "
+                                 f"non-negative, but it is {lo}.")
+            if hi < 0:
+                raise ValueError("Expected the maximum distance for this frame pair "
+                                 f"to non-negative, but it is {hi}.")
+            if lo > hi:
+                raise ValueError("Expected the minimum distance for this frame pair "
+                                 "to be less than or equal to the maximum distance, "
+                                 f"but they are {lo} and {hi}, respectively.")
+            pairs.append((frames, lo, hi))
+        kinds = {"none": abi.MH_PATH_FRAME_DISTANCE, "vector": abi.MH_PATH_FRAME_DISTANCE_VECTOR,
+                 "plane": abi.MH_PATH_FRAME_DISTANCE_PLANE}
+        if pc.projection not in kinds:
+            raise ValueError("Expected 'projection' to be 'none', 'vector', or 'plane', but "
+                             f"got '{pc.projection}'.")
+        n = [0.0, 0.0, 0.0]
+        if pc.projection != "none":
+            if pc.projection_vector is None or len(pc.projection_vector) == 0:
+                raise ValueError("Must provide a value for 'projection_vector'.")
+            if not any(float(v) != 0.0 for v in pc.projection_vector):
+                raise ValueError("'projection_vector' must not be the zero vector.")
+            n = unit3(pc.projection_vector)   # SimTK::UnitVec3
+        for (f1, f2), lo, hi in pairs:
+            e = abi.mh_path_equation()
+            e.kind = kinds[pc.projection]
+            e.index = e.table = -1   # the bodies and the term offset: ProblemRep.__init__
+            e.g.lower, e.g.upper = lo * lo, hi * hi
+            eqs.append(e)
+            frame_terms.append((f1[0], f2[0], list(f1[1]) + list(f2[1]) + n))

@@ -440,6 +440,16 @@ class _NLPBase:
         self._check(self._fn("eval_dae")(self.ctx, npts, abi.dptr(inputs), abi.dptr(out)))
         return out
 
+    def eval_path(self, inputs: np.ndarray) -> np.ndarray:
+        """Per-point path callback: rows [t, states, controls, derivatives,
+        ...] -> the path-equation values (mh_eval_path)."""
+        inputs = np.ascontiguousarray(inputs, float)
+        npts = inputs.shape[0]
+        assert inputs.shape[1] == 1 + self.NI
+        out = np.empty((npts, self.rep.num_path_equations))
+        self._check(self._fn("eval_path")(self.ctx, npts, abi.dptr(inputs), abi.dptr(out)))
+        return out
+
 class HipBatch:
     """mh_batch: structurally identical HipNLPs evaluated by one launch per
     kernel (include/mocohip.h mh_batch_*).  Calls take one device pointer
