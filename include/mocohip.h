@@ -325,11 +325,35 @@ enum mh_goal_kind {
      * when mh_options.minimize_lagrange_multipliers is set (weight
      * lagrange_multiplier_weight); its gradient is exact (the reference
      * differentiates this MX expression with AD, not by finite differences). */
-    MH_GOAL_LAGRANGE_MULTIPLIERS = 6
+    MH_GOAL_LAGRANGE_MULTIPLIERS = 6,
+    /* MocoMarkerTrackingGoal (MocoMarkerTrackingGoal.cpp:85-107): weight *
+     * duration * quadrature over every grid point of
+     *     L(t, q) = sum over the tracked markers m, in order, of
+     *               w_m * |p_G(marker m; q) - ref_m(t)|^2
+     * (states required; not with prescribed kinematics; nq <= 64).  `table` =
+     * the reference table (the piecewise polynomial of the flattened marker
+     * table, built as the state-tracking reference is).  Four consecutive
+     * terms per marker: in terms one to three goal_index = the marker's body
+     * (mh_model body index, -1 = ground), goal_column = the table's x / y / z
+     * column of the marker, goal_weight = the marker's location in its body
+     * frame (x, y, z); in term four goal_index = the same body, goal_column =
+     * -1, goal_weight = the marker weight w_m (>= 0).  Per marker, each
+     * operation rounded on its own (no fused multiply-add):
+     *     p_c = pose.p[c] + ((R[c][0] x + R[c][1] y) + R[c][2] z)  (ground: the
+     *                                                              location)
+     *     d_c = p_c - ref_c(t),  s = (d_0 d_0 + d_1 d_1) + d_2 d_2
+     *     L  += w_m * s                                  (from L = 0.0)
+     * Its gradient is the finite difference of the whole integrand (the
+     * CasADi FD of the cost-integrand callback, CasOCFunction.h:38-44) with
+     * k_grad's formulas: over t (the t0 / tf entries, seeds 1 - g and g) and
+     * over the coordinates on some tracked marker's ancestor chain; along
+     * every other input the integrand does not change and the quotient is
+     * exactly 0. */
+    MH_GOAL_MARKER_TRACKING = 7
 };
 typedef struct mh_goal {
     int32_t kind;
-    int32_t table;       /* state tracking: reference table                */
+    int32_t table;       /* state / marker tracking: reference table       */
     int32_t term_begin;  /* into mh_problem.goal_index / goal_weight       */
     int32_t term_count;  /* control: #controls weighted; tracking: #states */
     int32_t exponent;    /* control goal exponent (>=2)                    */

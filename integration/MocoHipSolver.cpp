@@ -31,6 +31,7 @@
 #include <OpenSim/Moco/MocoGoal/MocoControlGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoInitialActivationGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoMarkerFinalGoal.h>
+#include <OpenSim/Moco/MocoGoal/MocoMarkerTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoStateTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoSumSquaredStateGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoGoal.h>
@@ -492,6 +493,29 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
             hg.kind = mhb::Goal::MARKER_FINAL;
             hg.point_name = mf->get_point_name();
             for (int d = 0; d < 3; ++d) hg.reference_location[d] = mf->get_reference_location()[d];
+        } else if (const auto* mt = dynamic_cast<const MocoMarkerTrackingGoal*>(&g)) {
+            // the flattened marker table (columns <label>_1, _2, _3) as a
+            // model table, splined as GCVSplineSet(table) does (degree 5);
+            // the labels with their weights by reference index --
+            // mhb::make_rep runs initializeOnModelImpl's checks.  (A
+            // reference given as a marker file is expected to be loaded:
+            // the goal loads it in initializeOnModelImpl, which has run on
+            // this MocoProblemRep.)
+            hg.kind = mhb::Goal::MARKER_TRACKING;
+            const MarkersReference& mref = mt->getMarkersReference();
+            hg.table = "markers_reference_" + g.getName();
+            // (the goal has a setter only, and its property accessors are
+            // protected: read the property by name)
+            hg.allow_unused_references = mt->getPropertyByName("allow_unused_references").getValue<bool>();
+            const auto& names = mref.getNames();
+            SimTK::Array_<double> weights;
+            mref.getWeights(model.getWorkingState(), weights);
+            for (int i = 0; i < (int)names.size(); ++i) hg.weights.push_back({names[i], weights[i]});
+            std::vector<std::string> sorted(names.begin(), names.end());
+            std::sort(sorted.begin(), sorted.end());
+            // (a redundant label cannot be flattened; make_rep reports it)
+            if (std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end())
+                prob.model.add_table(toTable(hg.table, mref.getMarkerTable().flatten(), 5));
         } else {
             OPENSIM_THROW(Exception, "MocoHipSolver: goal '{}' of type '{}' is not supported (SURVEY §8 A11)",
                     g.getName(), g.getConcreteClassName());

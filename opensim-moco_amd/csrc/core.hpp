@@ -2054,9 +2054,10 @@ __device__ __forceinline__ void gather_inputs(const double* __restrict__ x, cons
 }
 
 // Goals with an integral (quadrature of an integrand): all but the endpoint
-// costs (final time, final marker).
+// costs (final time, final marker) and the marker-tracking goal, whose
+// integrand and gradient k_marker_tracking writes into the same slots.
 __host__ __device__ __forceinline__ bool goal_integral(int kind) {
-    return kind != MH_GOAL_FINAL_TIME && kind != MH_GOAL_MARKER_FINAL;
+    return kind != MH_GOAL_FINAL_TIME && kind != MH_GOAL_MARKER_FINAL && kind != MH_GOAL_MARKER_TRACKING;
 }
 constexpr int MH_MARKER_MAX_Q = 64;   // coordinates a marker goal's kernel holds per lane
 
@@ -2068,6 +2069,35 @@ struct GoalSet {
     const int* gidx;
     const int* gcol;
     const double* gw;
+};
+
+// Marker-tracking goals (MH_GOAL_MARKER_TRACKING) as k_marker_tracking reads
+// them: the markers of all such goals in goal order, goal j's being
+// mbegin[j] .. mbegin[j + 1].  tab has FrameDist's layout (one body per
+// marker where FrameDist has two per equation): [nm] slot of each marker's
+// body (-1: ground), [2 nslots] begin / count of each slot's chain in the body
+// list, [nq] lane index l of each coordinate (-1: on no tracked chain), [nlc]
+// coordinate of lane l, the chains' bodies root first; then [nm] the first of
+// each marker's four terms, [ntg] each goal's index in the GoalSet, [ntg + 1]
+// mbegin, [nlc][nslots] whether lane l's coordinate drives a body of the
+// slot's chain.
+struct MarkerTrack {
+    const int* __restrict__ tab;
+    int nm;          // tracked markers (0: no such goal)
+    int ntg;         // marker-tracking goals
+    int nslots;      // distinct bodies that carry a tracked marker
+    int nlc;         // coordinates with lanes
+    int nq;
+    int nchain;      // bodies in all chains
+    __device__ __forceinline__ const int* slot() const { return tab; }
+    __device__ __forceinline__ const int* chain() const { return tab + nm; }
+    __device__ __forceinline__ const int* lane() const { return tab + nm + 2 * nslots; }
+    __device__ __forceinline__ const int* coord() const { return lane() + nq; }
+    __device__ __forceinline__ const int* bodies() const { return coord() + nlc; }
+    __device__ __forceinline__ const int* term() const { return bodies() + nchain; }
+    __device__ __forceinline__ const int* goal() const { return term() + nm; }
+    __device__ __forceinline__ const int* mbegin() const { return goal() + ntg; }
+    __device__ __forceinline__ const int* on_chain() const { return mbegin() + ntg + 1; }
 };
 
 __device__ double goal_integrand(const DevModel& M, const GoalSet& GS, int g, double t,
@@ -2362,6 +2392,11 @@ struct mh_ctx {
     double* d_xch = nullptr;       // k_role -> k_couple exchange [interval][point][NO][3]
     double* d_ep = nullptr;        // endpoint-cost values per goal (k_marker_final)
     bool has_marker = false;
+    // marker-tracking goals (MarkerTrack): the int table as uploaded and the
+    // dynamic LDS of k_marker_tracking in objective / gradient mode
+    MarkerTrack MT{};
+    std::vector<int> mt_tab;
+    size_t mt_lds[2] = {0, 0};
     bool use_roles = false;        // MOCOHIP_ROLES=1: k_role (+ k_couple) for the Jacobian lanes
     int role_threads = 256;        // k_role workgroup size (MOCOHIP_ROLE_THREADS: 64..512)
     int iv_threads = 1024;         // k_interval workgroup size, Jacobian lanes (MOCOHIP_IV_THREADS: 256..1024)

@@ -830,6 +830,48 @@ void make_rep(const Problem& P, ProblemRep& R) {
             for (int c = 0; c < 3; ++c) term(body, 3 + c, g.reference_location[c]);
             break;
         }
+        case Goal::MARKER_TRACKING: {
+            // MocoMarkerTrackingGoal::initializeOnModelImpl
+            // (MocoMarkerTrackingGoal.cpp:28-83; problem.py
+            // _marker_tracking_terms): four terms per tracked marker
+            if (presc)
+                fail("MocoMarkerTrackingGoal with prescribed kinematics (the coordinates are not NLP states)");
+            gs.kind = MH_GOAL_MARKER_TRACKING;
+            std::vector<std::string> labels;
+            for (auto& kv : g.weights) labels.push_back(kv.first);
+            std::sort(labels.begin(), labels.end());   // checkRedundantLabels
+            auto dup = std::adjacent_find(labels.begin(), labels.end());
+            if (dup != labels.end()) fail("Label '" + *dup + "' appears more than once.");
+            const int ti = lookup(R.cm.table_index, g.table);
+            if (ti < 0) fail("reference table " + g.table + " not in model");
+            gs.table = R.cm.table_index[ti].second;
+            const auto& cols = R.cm.table_columns[lookup(R.cm.table_columns, g.table)].second;
+            for (auto& kv : g.weights) {
+                const Marker* mk = nullptr;
+                for (auto& x : model.markers)
+                    if (x.path == kv.first) { mk = &x; break; }     // a component path ...
+                if (!mk)
+                    for (auto& x : model.markers)
+                        if (x.name == kv.first) { mk = &x; break; } // ... or a name in the marker set
+                if (!mk) {
+                    if (!g.allow_unused_references)
+                        fail("Marker '" + kv.first + "' unrecognized by the specified model.");
+                    continue;
+                }
+                if (kv.second < 0)
+                    fail("MocoMarkerTrackingGoal: negative weight " + num(kv.second) + " of marker '" + kv.first +
+                         "'");
+                const int body = R.cm.index_of_body(mk->body);
+                for (int c = 0; c < 3; ++c) {
+                    const std::string col = kv.first + "_" + std::to_string(c + 1);
+                    auto it = std::find(cols.begin(), cols.end(), col);
+                    if (it == cols.end()) fail("reference table " + g.table + " has no column '" + col + "'");
+                    term(body, (int)(it - cols.begin()), mk->location[c]);
+                }
+                term(body, -1, kv.second);
+            }
+            break;
+        }
         case Goal::AUX_DERIVATIVES: {
             gs.kind = MH_GOAL_AUX_DERIVATIVES;
             int naux = 0;
@@ -1340,6 +1382,10 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
             } else if (kind == "marker_final") {
                 g.kind = Goal::MARKER_FINAL;
                 g.name = t.s(); g.weight = t.d(); g.point_name = t.s(); t.d3(g.reference_location);
+            } else if (kind == "marker_tracking") {
+                g.kind = Goal::MARKER_TRACKING;
+                g.name = t.s(); g.weight = t.d(); g.table = t.s(); g.allow_unused_references = t.i() != 0;
+                g.weights = read_weights(t);
             } else if (kind == "aux_derivatives") {
                 g.kind = Goal::AUX_DERIVATIVES;
                 g.name = t.s(); g.weight = t.d();

@@ -244,13 +244,18 @@ struct VariableInfo {
 
 struct Goal {
     enum Kind { CONTROL, STATE_TRACKING, FINAL_TIME, SUM_SQUARED_STATE, INITIAL_ACTIVATION, MARKER_FINAL,
-                AUX_DERIVATIVES };
+                AUX_DERIVATIVES, MARKER_TRACKING };
     Kind kind = CONTROL;
     std::string name;
     double weight = 1.0;
     int exponent = 2;
-    std::vector<std::pair<std::string, double>> weights;   // control / state weights
-    std::string table;                                      // state tracking reference
+    // control / state weights; marker tracking: the reference's labels with
+    // their weights, by reference index
+    std::vector<std::pair<std::string, double>> weights;
+    // state tracking reference; marker tracking: the flattened markers table
+    // (columns <label>_1, _2, _3), one of the model's tables
+    std::string table;
+    bool allow_unused_references = false;                   // marker tracking
     std::string mode = "endpoint_constraint";               // initial activation
     std::string point_name;                                 // marker final
     double reference_location[3] = {0, 0, 0};

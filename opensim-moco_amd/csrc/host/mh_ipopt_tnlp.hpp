@@ -36,6 +36,7 @@ struct IpoptSettings {
     double optim_constraint_tolerance = -1.0;
     std::string optim_hessian_approximation = "limited-memory";
     int optim_ipopt_print_level = -1;
+    int optim_ipopt_limited_memory_max_history = -1;   // -1: Ipopt's default (6)
 };
 
 // MocoCasADiSolver.cpp:218-246.
@@ -45,6 +46,8 @@ inline void apply_ipopt_options(Ipopt::IpoptApplication& app, const IpoptSetting
     if (s.verbosity < 2) opts->SetIntegerValue("print_level", 0);
     else if (s.optim_ipopt_print_level != -1) opts->SetIntegerValue("print_level", s.optim_ipopt_print_level);
     opts->SetStringValue("hessian_approximation", s.optim_hessian_approximation);
+    if (s.optim_ipopt_limited_memory_max_history != -1)
+        opts->SetIntegerValue("limited_memory_max_history", s.optim_ipopt_limited_memory_max_history);
     if (s.optim_max_iterations != -1) opts->SetIntegerValue("max_iter", s.optim_max_iterations);
     if (s.optim_convergence_tolerance != -1) {
         const double tol = s.optim_convergence_tolerance;   // as Simbody does

@@ -21,6 +21,7 @@
 //                 and CasADi's finite-difference quotients; plus one block
 //                 per interval for the defect / interpolation rows of g.
 //   k_integrand / k_grad / k_reduce_obj : objective and its gradient.
+//   k_marker_final / k_marker_tracking : the marker goals (body kinematics).
 //
 // There is no CPU fallback anywhere in this file.
 #include "core.hpp"
@@ -588,6 +589,118 @@ __global__ void __launch_bounds__(128) k_marker_final(DevModel M, Layout L, Goal
         const double d = fd == MH_FD_CENTRAL ? (cost[1 + s] - cost[1 + NQ + s]) / (2.0 * h)
                        : (fd == MH_FD_FORWARD ? (cost[1 + s] - cost[0]) / h : (cost[0] - cost[1 + s]) / h);
         grad[2 + (long)(L.G - 1) * L.NS + s] += G.weight * d;
+    }
+}
+
+// MocoMarkerTrackingGoal (MocoMarkerTrackingGoal.cpp:85-107; include/mocohip.h
+// MH_GOAL_MARKER_TRACKING): block = grid point k, all of them.  mode 0: the
+// integrand, C[k * ngoals + gi] = quad[k] * L.  mode 1 (gradient) also the
+// finite-difference quotients of the whole integrand with k_grad's formulas
+// and arithmetic, added to what k_grad left in grad's coordinate entries of
+// point k and in tpart[k * 2 + {0, 1}]; every entry has one writer.
+// Lanes: 0 the point itself; 1 + l coordinate coord[l] moved by +h (backward
+// differences: -h), central differences also 1 + nlc + l by -h; then the time
+// lanes, t moved by +-h (1 - g) and +-h g in k_grad's order (d = 0, 1; central:
+// the two + lanes, then the two - lanes).  Time lanes move only the reference.
+// Phase 1: the pose of each distinct body at lane 0 and at every coordinate
+// lane whose coordinate is on the body's chain (MarkerTrack::on_chain; LDS, 12
+// doubles), and the
+// reference of every marker at the base and the time lanes' times.
+// Phase 2: thread = (lane, marker): the squared distance, from the lane's
+// pose where phase 1 wrote one and lane 0's otherwise -- a marker off the
+// perturbed chain gives both sides of the quotient the same bits.
+// Phase 3: thread = (lane, goal) sums the goal's markers in order; then
+// thread = direction forms the quotients.
+__global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, GoalSet GS, MarkerTrack T, int fd,
+        double h, int mode, const double* __restrict__ x, const double* __restrict__ grid,
+        const double* __restrict__ quad, double* __restrict__ C, double* __restrict__ grad,
+        double* __restrict__ tpart) {
+#pragma clang fp contract(off)
+    extern __shared__ double mt_lds[];
+    const int k = blockIdx.x;
+    const int ns = T.nslots, nm = T.nm, nlc = T.nlc, ntg = T.ntg;
+    const int sides = fd == MH_FD_CENTRAL ? 2 : 1;
+    const int npl = 1 + (mode ? sides * nlc : 0);   // lanes with poses of their own
+    const int nt = mode ? 2 * sides : 0;            // time lanes
+    const int nl = npl + nt;
+    double* pose = mt_lds;                          // [npl][slot][12]
+    double* ref = pose + (long)npl * ns * 12;       // [1 + nt][marker][3]
+    double* sq = ref + (long)(1 + nt) * nm * 3;     // [lane][marker]
+    double* Lv = sq + (long)nl * nm;                // [lane][goal]
+    const double g = grid[k], dur = x[1] - x[0], t = dur * g + x[0];
+    const double* q = x + 2 + (long)k * L.NS;
+    for (int w = threadIdx.x; w < npl * ns; w += blockDim.x) {
+        const int pl = w / ns, sl = w - pl * ns;
+        QLane Q{q, -1, 0.0};
+        if (pl > 0) {
+            const int l = (pl - 1) % nlc;
+            if (!T.on_chain()[l * ns + sl]) continue;   // phase 2 reads lane 0's pose
+            Q.s = T.coord()[l];
+            Q.d = fd == MH_FD_BACKWARD || pl > nlc ? -h : h;
+        }
+        const int cb = T.chain()[2 * sl], cn = T.chain()[2 * sl + 1];
+        const int* bodies = T.bodies() + cb;
+        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
+        for (int ci = 0; ci < cn; ++ci) joint_pose(M, Q, M.bodies[bodies[ci]], R, p);
+        double* o = pose + (long)w * 12;
+        for (int i = 0; i < 9; ++i) o[i] = R[i];
+        for (int i = 0; i < 3; ++i) o[9 + i] = p[i];
+    }
+    for (int w = threadIdx.x; w < (1 + nt) * nm * 3; w += blockDim.x) {
+        const int tl = w / (3 * nm), r = w - tl * 3 * nm, m = r / 3, c = r - 3 * m;
+        double tt = t;
+        if (tl > 0) {
+            const int d = (tl - 1) & 1;
+            const double seed = d == 0 ? 1.0 - g : g;
+            tt = fd == MH_FD_BACKWARD || tl - 1 >= 2 ? t - h * seed : t + h * seed;
+        }
+        // the goal of marker m: the one whose marker range holds it
+        int j = 0;
+        while (j + 1 < ntg && T.mbegin()[j + 1] <= m) ++j;
+        ref[w] = table_eval(M, GS.goals[T.goal()[j]].table, GS.gcol[T.term()[m] + c], tt);
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < nl * nm; w += blockDim.x) {
+        const int ln = w / nm, m = w - ln * nm;
+        const int tl = ln < npl ? 0 : ln - npl + 1;
+        const int sl = T.slot()[m];
+        const double* w3 = GS.gw + T.term()[m];
+        double p0 = w3[0], p1 = w3[1], p2 = w3[2];
+        if (sl >= 0) {
+            int pl = ln < npl ? ln : 0;
+            if (pl > 0 && !T.on_chain()[(pl - 1) % nlc * ns + sl]) pl = 0;
+            const double* A = pose + ((long)pl * ns + sl) * 12;
+            p0 = A[9] + ((A[0] * w3[0] + A[1] * w3[1]) + A[2] * w3[2]);
+            p1 = A[10] + ((A[3] * w3[0] + A[4] * w3[1]) + A[5] * w3[2]);
+            p2 = A[11] + ((A[6] * w3[0] + A[7] * w3[1]) + A[8] * w3[2]);
+        }
+        const double* rf = ref + ((long)tl * nm + m) * 3;
+        const double d0 = p0 - rf[0], d1 = p1 - rf[1], d2 = p2 - rf[2];
+        sq[w] = (d0 * d0 + d1 * d1) + d2 * d2;
+    }
+    __syncthreads();
+    for (int w = threadIdx.x; w < nl * ntg; w += blockDim.x) {
+        const int ln = w / ntg, j = w - ln * ntg;
+        double s = 0.0;
+        for (int m = T.mbegin()[j]; m < T.mbegin()[j + 1]; ++m) s += GS.gw[T.term()[m] + 3] * sq[(long)ln * nm + m];
+        Lv[w] = s;
+    }
+    __syncthreads();
+    for (int j = threadIdx.x; j < ntg; j += blockDim.x) C[(long)k * GS.ngoals + T.goal()[j]] = quad[k] * Lv[j];
+    if (!mode) return;
+    for (int d = threadIdx.x; d < 2 + nlc; d += blockDim.x) {
+        const int la = d < 2 ? npl + d : 1 + (d - 2);             // +h (backward: -h)
+        const int lb = d < 2 ? npl + 2 + d : 1 + nlc + (d - 2);   // -h, central only
+        double acc = 0.0;
+        for (int j = 0; j < ntg; ++j) {
+            const mh_goal G = GS.goals[T.goal()[j]];
+            const double l0 = Lv[j], l1 = Lv[(long)la * ntg + j];
+            const double dL = fd == MH_FD_CENTRAL ? (l1 - Lv[(long)lb * ntg + j]) / (2.0 * h)
+                            : (fd == MH_FD_FORWARD ? (l1 - l0) / h : (l0 - l1) / h);
+            acc += G.weight * dur * quad[k] * dL;
+        }
+        if (d < 2) tpart[(long)k * 2 + d] += acc;
+        else grad[2 + (long)k * L.NS + T.coord()[d - 2]] += acc;
     }
 }
 
@@ -1562,14 +1675,16 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
     // (a bad index would be an out-of-bounds device read)
     for (int g = 0; g < p->ngoals; ++g) {
         const mh_goal& G = p->goals[g];
-        if (G.kind < MH_GOAL_CONTROL || G.kind > MH_GOAL_MARKER_FINAL)
+        const bool tracking = G.kind == MH_GOAL_MARKER_TRACKING;
+        const bool marker = G.kind == MH_GOAL_MARKER_FINAL || tracking;
+        if (G.kind < MH_GOAL_CONTROL || (G.kind > MH_GOAL_MARKER_FINAL && !tracking))
             return set_err(MH_ERR_INVALID, "goal %d: unknown kind %d", g, G.kind);
-        if (G.term_begin < 0 || G.term_count < 0 || G.term_begin + G.term_count > p->nterms ||
-                (G.kind == MH_GOAL_MARKER_FINAL && G.term_count != 6))
+        if (G.term_begin < 0 || G.term_count < 0 || (int64_t)G.term_begin + G.term_count > p->nterms ||
+                (G.kind == MH_GOAL_MARKER_FINAL && G.term_count != 6) || (tracking && G.term_count % 4 != 0))
             return set_err(MH_ERR_INVALID, "goal %d: bad terms", g);
-        if (G.kind == MH_GOAL_STATE_TRACKING && (G.table < 0 || G.table >= M.ntables))
+        if ((G.kind == MH_GOAL_STATE_TRACKING || tracking) && (G.table < 0 || G.table >= M.ntables))
             return set_err(MH_ERR_INVALID, "goal %d: bad table", g);
-        if (G.kind == MH_GOAL_MARKER_FINAL && (c->presc || M.nq > MH_MARKER_MAX_Q))
+        if (marker && (c->presc || M.nq > MH_MARKER_MAX_Q))
             return set_err(MH_ERR_UNSUPPORTED, "goal %d: marker goal needs coordinate states (<= %d)", g,
                     MH_MARKER_MAX_Q);
         for (int k = G.term_begin; k < G.term_begin + G.term_count; ++k) {
@@ -1579,14 +1694,18 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
             case MH_GOAL_CONTROL: hi = c->NC; break;
             case MH_GOAL_STATE_TRACKING: case MH_GOAL_SUM_SQUARED_STATE: hi = c->NS; break;
             case MH_GOAL_AUX_DERIVATIVES: hi = c->NAR; break;
-            case MH_GOAL_MARKER_FINAL: hi = M.nbodies; break;
+            case MH_GOAL_MARKER_FINAL: case MH_GOAL_MARKER_TRACKING: hi = M.nbodies; break;
             default: hi = INT32_MAX; break;   // final time: no terms read
             }
-            if (idx < (G.kind == MH_GOAL_MARKER_FINAL ? -1 : 0) || idx >= hi)
+            if (idx < (marker ? -1 : 0) || idx >= hi)
                 return set_err(MH_ERR_INVALID, "goal %d: term %d index %d out of range", g, k, idx);
-            if (G.kind == MH_GOAL_STATE_TRACKING &&
-                    (p->goal_column[k] < 0 || p->goal_column[k] >= M.tables[G.table].ncol))
+            const bool column = G.kind == MH_GOAL_STATE_TRACKING || (tracking && (k - G.term_begin) % 4 != 3);
+            if (column && (p->goal_column[k] < 0 || p->goal_column[k] >= M.tables[G.table].ncol))
                 return set_err(MH_ERR_INVALID, "goal %d: term %d column out of range", g, k);
+            if (tracking && (k - G.term_begin) % 4 == 3 && !(p->goal_weight[k] >= 0.0))
+                return set_err(MH_ERR_INVALID, "goal %d: term %d: negative marker weight", g, k);
+            if (tracking && idx != p->goal_index[k - (k - G.term_begin) % 4])
+                return set_err(MH_ERR_INVALID, "goal %d: term %d: a marker's terms name different bodies", g, k);
         }
     }
     for (int e = 0; e < M.nexternal; ++e) {
@@ -1750,13 +1869,20 @@ static int build_seeds(mh_ctx* c);
 static const TaskInfo* backend_tasks(const Backend* b);
 static bool interval_fits(const mh_ctx* c, int mode);
 
-// FrameDist's int table (core.hpp) and counts for the frame-distance
-// equations of c->pc: one slot per distinct body, its ancestor chain root
-// first, and a lane for every coordinate that drives a body of some chain.
-static FrameDist frame_distance_tables(mh_ctx* c, const mh_model& M, const std::vector<int>& coord_body) {
-    FrameDist F{};
-    if (!c->has_fdist) return F;
-    std::vector<int> slot(2 * (size_t)c->npc, -1), slot_body, chain, bodies;
+// The int table FrameDist and MarkerTrack share (core.hpp), for the bodies
+// ref_body names (-1: ground, or no body): [refs] slot of each reference's
+// body (-1: none), one slot per distinct body; [2 nslots] begin / count of
+// each slot's ancestor chain in the body list; [nq] lane index of every
+// coordinate that drives a body of some chain (-1: of none); [nlc] the lanes'
+// coordinates; the chains' bodies, root first.
+struct ChainTables {
+    std::vector<int> tab;
+    int nslots = 0, nlc = 0, nchain = 0;
+};
+static ChainTables body_chain_tables(const mh_model& M, const std::vector<int>& coord_body,
+        const std::vector<int>& ref_body) {
+    ChainTables T;
+    std::vector<int> slot(ref_body.size(), -1), slot_body, chain, bodies;
     auto slot_of = [&](int b) {
         if (b < 0) return -1;
         for (size_t i = 0; i < slot_body.size(); ++i)
@@ -1764,11 +1890,7 @@ static FrameDist frame_distance_tables(mh_ctx* c, const mh_model& M, const std::
         slot_body.push_back(b);
         return (int)slot_body.size() - 1;
     };
-    for (int e = 0; e < c->npc; ++e) {
-        if (c->pc[e].kind == MH_PATH_CONTROL_BOUND) continue;
-        slot[2 * e] = slot_of(c->pc[e].index);
-        slot[2 * e + 1] = slot_of(c->pc[e].table);
-    }
+    for (size_t r = 0; r < ref_body.size(); ++r) slot[r] = slot_of(ref_body[r]);
     std::vector<char> on_chain(M.nbodies, 0);
     for (int b : slot_body) {
         std::vector<int> up;
@@ -1780,19 +1902,84 @@ static FrameDist frame_distance_tables(mh_ctx* c, const mh_model& M, const std::
     std::vector<int> lane(M.nq, -1), coord;
     for (int j = 0; j < M.nq; ++j)
         if (on_chain[coord_body[j]]) { lane[j] = (int)coord.size(); coord.push_back(j); }
-    F.nslots = (int)slot_body.size();
-    F.nlc = (int)coord.size();
+    T.nslots = (int)slot_body.size();
+    T.nlc = (int)coord.size();
+    T.nchain = (int)bodies.size();
+    T.tab = slot;
+    T.tab.insert(T.tab.end(), chain.begin(), chain.end());
+    T.tab.insert(T.tab.end(), lane.begin(), lane.end());
+    T.tab.insert(T.tab.end(), coord.begin(), coord.end());
+    T.tab.insert(T.tab.end(), bodies.begin(), bodies.end());
+    return T;
+}
+
+// FrameDist's int table (core.hpp) and counts for the frame-distance
+// equations of c->pc.
+static FrameDist frame_distance_tables(mh_ctx* c, const mh_model& M, const std::vector<int>& coord_body) {
+    FrameDist F{};
+    if (!c->has_fdist) return F;
+    std::vector<int> ref_body(2 * (size_t)c->npc, -1);
+    for (int e = 0; e < c->npc; ++e) {
+        if (c->pc[e].kind == MH_PATH_CONTROL_BOUND) continue;
+        ref_body[2 * e] = c->pc[e].index;
+        ref_body[2 * e + 1] = c->pc[e].table;
+    }
+    ChainTables T = body_chain_tables(M, coord_body, ref_body);
+    F.nslots = T.nslots;
+    F.nlc = T.nlc;
     F.nl = 1 + (c->fd == MH_FD_CENTRAL ? 2 : 1) * F.nlc;
     F.nq = M.nq;
     F.k0 = c->k0;
     F.kshift = c->scheme == MH_HERMITE_SIMPSON ? 1 : 0;
-    c->fd_tab = slot;
-    c->fd_tab.insert(c->fd_tab.end(), chain.begin(), chain.end());
-    c->fd_tab.insert(c->fd_tab.end(), lane.begin(), lane.end());
-    c->fd_tab.insert(c->fd_tab.end(), coord.begin(), coord.end());
-    c->fd_tab.insert(c->fd_tab.end(), bodies.begin(), bodies.end());
+    c->fd_tab = std::move(T.tab);
     c->fd_lds = sizeof(double) * 12 * (size_t)F.nl * std::max(1, F.nslots);
     return F;
+}
+
+// MarkerTrack's int table (core.hpp) and counts for the marker-tracking goals
+// of c->goals, and k_marker_tracking's LDS in both modes (its layout).
+static MarkerTrack marker_tracking_tables(mh_ctx* c, const mh_model& M, const std::vector<int>& coord_body) {
+    MarkerTrack T{};
+    std::vector<int> ref_body, term, goal, mbegin;
+    for (size_t g = 0; g < c->goals.size(); ++g) {
+        const mh_goal& G = c->goals[g];
+        if (G.kind != MH_GOAL_MARKER_TRACKING) continue;
+        goal.push_back((int)g);
+        mbegin.push_back((int)term.size());
+        for (int k = G.term_begin; k < G.term_begin + G.term_count; k += 4) {
+            ref_body.push_back(c->gidx[k]);
+            term.push_back(k);
+        }
+    }
+    if (goal.empty()) return T;
+    mbegin.push_back((int)term.size());
+    ChainTables B = body_chain_tables(M, coord_body, ref_body);
+    T.nm = (int)term.size();
+    T.ntg = (int)goal.size();
+    T.nslots = B.nslots;
+    T.nlc = B.nlc;
+    T.nq = M.nq;
+    T.nchain = B.nchain;
+    c->mt_tab = B.tab;
+    c->mt_tab.insert(c->mt_tab.end(), term.begin(), term.end());
+    c->mt_tab.insert(c->mt_tab.end(), goal.begin(), goal.end());
+    c->mt_tab.insert(c->mt_tab.end(), mbegin.begin(), mbegin.end());
+    // on_chain[l][slot]: coordinate coord[l] drives a body of the slot's chain
+    // (B.tab: slots, chains, lanes, coordinates, bodies)
+    const int* chain = B.tab.data() + T.nm;
+    const int* coord = chain + 2 * T.nslots + T.nq;
+    const int* bodies = coord + T.nlc;
+    for (int l = 0; l < T.nlc; ++l)
+        for (int sl = 0; sl < T.nslots; ++sl) {
+            const int* cb = bodies + chain[2 * sl];
+            c->mt_tab.push_back(std::find(cb, cb + chain[2 * sl + 1], coord_body[coord[l]]) != cb + chain[2 * sl + 1]);
+        }
+    const size_t sides = c->fd == MH_FD_CENTRAL ? 2 : 1;
+    for (int mode = 0; mode < 2; ++mode) {
+        const size_t npl = 1 + (mode ? sides * T.nlc : 0), nt = mode ? 2 * sides : 0, nl = npl + nt;
+        c->mt_lds[mode] = sizeof(double) * (12 * npl * T.nslots + 3 * (1 + nt) * T.nm + nl * T.nm + nl * T.ntg);
+    }
+    return T;
 }
 
 extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out) {
@@ -1845,8 +2032,13 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     FrameDist FD = frame_distance_tables(c.get(), M, coord_body);
     if (c->fd_lds > 64 * 1024)
         return set_err(MH_ERR_UNSUPPORTED, "frame distance: %d bodies x %d lanes exceed the LDS", FD.nslots, FD.nl);
+    MarkerTrack MT = marker_tracking_tables(c.get(), M, coord_body);
+    if (c->mt_lds[1] > 64 * 1024)
+        return set_err(MH_ERR_UNSUPPORTED, "marker tracking: %d markers on %d bodies x %d coordinate lanes exceed "
+                       "the LDS", MT.nm, MT.nslots, MT.nlc);
     Arena A;
     const size_t o_fdtab = A.put(c->fd_tab.data(), c->fd_tab.size());
+    const size_t o_mttab = A.put(c->mt_tab.data(), c->mt_tab.size());
     const size_t o_bodies = A.put(M.bodies, M.nbodies), o_axes = A.put(M.axes, M.naxes),
                  o_funcs = A.put(M.functions, M.nfunctions), o_kx = A.put(M.knot_x, M.nknots),
                  o_ky = A.put(M.knot_y, M.nknots), o_kb = A.put(kb.data(), kb.size()),
@@ -2158,6 +2350,8 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     c->d_ep = (double*)(b + o_epc);
     c->has_marker = false;
     for (int g = 0; g < p->ngoals; ++g) c->has_marker |= p->goals[g].kind == MH_GOAL_MARKER_FINAL;
+    if (MT.nm > 0) MT.tab = (const int*)(b + o_mttab);
+    c->MT = MT;
     c->d_xch = (double*)(b + o_xch);
     if (c->jac_seeds) {
         c->d_seed_cols = (int32_t*)(b + o_scol);
@@ -3143,6 +3337,15 @@ extern "C" int mh_eval_g_jac_g(mh_ctx* c, const double* x, double* g, double* va
     return finish(c);
 }
 
+// The marker-tracking goals' integrands (mode 0) and their gradient parts
+// (mode 1) at every grid point, with the quadrature weights c->d_quad points
+// at during the call (the shard's, for a partial).
+static void launch_marker_tracking(mh_ctx* c, const Layout& L, int mode) {
+    if (c->MT.nm == 0) return;
+    hipLaunchKernelGGL(k_marker_tracking, dim3((unsigned)c->G), dim3(128), c->mt_lds[mode], c->stream, c->M, L,
+            c->GS, c->MT, c->fd, c->h, mode, c->d_x, c->d_grid, c->d_quad, c->d_C, c->d_grad, c->d_tpart);
+}
+
 // The objective (partial = false) or this shard's partial of it (partial =
 // true: the integrals over the shard's own mesh intervals, d_quadp, and the
 // endpoint goals -- final time, final marker -- on the shard that owns the
@@ -3160,6 +3363,7 @@ static int eval_f_impl(mh_ctx* c, const double* x, double* f, bool partial) {
     if (partial) c->d_quad = c->d_quadp;
     Layout L = make_layout(c, 0, c->G);
     if (c->ngoals > 0) c->be->integrand(c, c->d_x);
+    launch_marker_tracking(c, L, 0);   // after k_integrand: the marker-tracking goals' slots
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)
@@ -3192,6 +3396,7 @@ static int eval_grad_f_impl(mh_ctx* c, const double* x, double* grad, bool parti
         c->be->integrand(c, c->d_x);
         c->be->grad(c, c->d_x);
     }
+    launch_marker_tracking(c, L, 1);   // after k_grad: adds to the coordinates' and the t0 / tf entries
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)   // after k_grad: adds to the final coordinates' entries
@@ -3228,6 +3433,7 @@ extern "C" int mh_eval_objective_terms(mh_ctx* c, const double* x, double* terms
     apply_params(c, c->d_x);   // the goals read the context's model, copy 0
     Layout L = make_layout(c, 0, c->G);
     c->be->integrand(c, c->d_x);
+    launch_marker_tracking(c, L, 0);
     HIPCHK(hipGetLastError());
     if (c->has_marker)
         hipLaunchKernelGGL(k_marker_final, dim3((unsigned)c->ngoals), dim3(128), 0, c->stream, c->M, L, c->GS,

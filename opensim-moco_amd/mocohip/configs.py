@@ -28,8 +28,8 @@ from .osim import add_reserves
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm,
                       MocoControlBoundConstraint, MocoControlGoal, MocoFrameDistanceConstraint,
                       MocoInitialActivationGoal,
-                      MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoProblem, MocoStateTrackingGoal,
-                      PiecewiseLinearFunction)
+                      MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoMarkerTrackingGoal, MarkersReference,
+                      MocoProblem, MocoStateTrackingGoal, PiecewiseLinearFunction)
 from .solver import MocoHipSolver, MocoStudy
 
 DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
@@ -412,6 +412,142 @@ def gimbal_frame_distance(num_mesh_intervals: int = 25, dynamics: str = "explici
     return MocoStudy(p, s)
 
 
+def double_pendulum_marker_tracking(num_mesh_intervals: int = 50, scheme: str = "hermite-simpson",
+                                    fd_scheme: str = "central") -> MocoStudy:
+    """exampleMarkerTracking.cpp:27-157: two links of mass 1 and inertia 1 on
+    pin joints (coordinates in [-10, 10], child frames at (-1, 0, 0)), torque
+    actuators with controls in [-40, 40], markers m0 / m1 at the body origins,
+    time [0, 1], and one MocoMarkerTrackingGoal whose reference rows at t = 0,
+    0.01, ..., 0.99 are the markers' locations for q0 = t pi / 2, q1 = t pi /
+    4, with marker weights 100 and 10; 50 mesh intervals, the solver's
+    defaults otherwise (Hermite-Simpson, central differences).  The example
+    solves with the exact Hessian (:147); this path has the limited-memory
+    approximation only, and with Ipopt's default memory of 6 pairs the
+    interior-point restatement crawls (no scheme converges within 3000
+    iterations), so the config keeps 100 pairs (marker
+    tracking)."""
+    m = Model("double_pendulum")
+    prev = "ground"
+    for i in range(2):
+        m.add_body(Body(f"b{i}", 1.0, (0, 0, 0), (1, 1, 1, 0, 0, 0)))
+        m.add_joint(Joint.pin(f"j{i}", prev, f"b{i}", Coordinate(f"q{i}", (-10, 10)), loc_in_child=(-1, 0, 0)))
+        prev = f"b{i}"
+    for i in range(2):
+        m.add_coordinate_actuator(CoordinateActuator(f"tau{i}", f"q{i}", 1.0, -40.0, 40.0, path=f"/tau{i}"))
+    for i in range(2):
+        m.add_marker(Marker(f"m{i}", f"b{i}", (0.0, 0.0, 0.0)))
+    times, rows = [], []
+    t = 0.0
+    while t < 1.0:   # for (double time = 0; time < finalTime; time += 0.01)
+        q0, q1 = (t / 1.0) * 0.5 * math.pi, (t / 1.0) * 0.25 * math.pi
+        m0 = (math.cos(q0), math.sin(q0), 0.0)
+        rows.append([m0, (m0[0] + math.cos(q0 + q1), m0[1] + math.sin(q0 + q1), 0.0)])
+        times.append(t)
+        t += 0.01
+    ref = MarkersReference("markers_reference", np.asarray(times), ["/markerset/m0", "/markerset/m1"],
+                           np.asarray(rows), {"/markerset/m0": 100.0, "/markerset/m1": 10.0})
+    m.add_table(ref.flatten())
+    p = MocoProblem(m)
+    p.set_time_bounds(0, 1.0)
+    p.add_goal(MocoMarkerTrackingGoal("marker_tracking", 1.0, ref))
+    s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals, transcription_scheme=scheme,
+                      optim_finite_difference_scheme=fd_scheme, optim_ipopt_limited_memory_max_history=100)
+    return MocoStudy(p, s)
+
+
+# The markers of the gait10dof18musc marker-tracking configs: (name, body,
+# location in the body frame, m).  The model data has none; these sit where a
+# gait marker set puts them (pelvis: the anterior and posterior superior iliac
+# spines' midpoints; thigh and shank: mid-segment, on the anterior / lateral
+# surface; the knee and ankle joint lines; heel and toe), at offsets rounded
+# from the segment geometry of the gait2392 family this model belongs to.
+GAIT_MARKERS = (
+    ("pelvis_front", "pelvis", (0.02, 0.03, 0.0)),
+    ("pelvis_back", "pelvis", (-0.15, 0.04, 0.0)),
+    ("thigh_r", "femur_r", (0.05, -0.2, 0.06)),
+    ("knee_r", "femur_r", (0.0, -0.4, 0.05)),
+    ("shank_r", "tibia_r", (0.03, -0.2, 0.05)),
+    ("ankle_r", "tibia_r", (-0.01, -0.4, 0.05)),
+    ("heel_r", "calcn_r", (-0.02, 0.02, 0.0)),
+    ("toe_r", "toes_r", (0.03, 0.01, 0.0)),
+    ("thigh_l", "femur_l", (0.05, -0.2, -0.06)),
+    ("knee_l", "femur_l", (0.0, -0.4, -0.05)),
+    ("shank_l", "tibia_l", (0.03, -0.2, -0.05)),
+    ("ankle_l", "tibia_l", (-0.01, -0.4, -0.05)),
+    ("heel_l", "calcn_l", (-0.02, 0.02, 0.0)),
+    ("toe_l", "toes_l", (0.03, 0.01, 0.0)),
+)
+
+
+def synthesize_markers_reference(m: Model, times, coordinate_columns,
+                                 name: str = "markers_reference") -> MarkersReference:
+    """The model's markers' trajectories (Model.marker_locations_in_ground)
+    along coordinate trajectories given by coordinate value path, as a
+    MarkersReference labelled by marker name."""
+    bypath = {c.path + "/value": c.name for c in m.coordinates()}
+    cols = {bypath[k]: np.asarray(v, float) for k, v in coordinate_columns.items() if k in bypath}
+    byname = {mk.name: path for path, mk in m.markers.items()}
+    labels = list(byname)
+    pos = np.empty((len(times), len(labels), 3))
+    for r in range(len(times)):
+        loc = m.marker_locations_in_ground({n: v[r] for n, v in cols.items()})
+        for i, n in enumerate(labels):
+            pos[r, i] = loc[byname[n]]
+    return MarkersReference(name, np.asarray(times, float), labels, pos)
+
+
+def gait10dof18musc_marker_track(num_mesh_intervals: int = 200, muscles: bool = True,
+                                 fd_scheme: str = "forward", dynamics: str = "explicit",
+                                 markers=GAIT_MARKERS, ground_marker: bool = False) -> MocoStudy:
+    """The gait10dof18musc study (configs[2]) in MocoTrack's marker mode
+    (MocoTrack::configureMarkerTracking, MocoTrack.cpp:235-266): the
+    state-tracking goal replaced by a MocoMarkerTrackingGoal "marker_tracking"
+    (weight 1, every marker weight 1), the control-effort goal (0.001) kept,
+    the time bounds the marker data's range, MocoTrack's solver settings.
+    The markers are GAIT_MARKERS; their trajectories are synthesized from the
+    bundled walking coordinate trajectories (walk_gait1018_state_reference) by
+    forward kinematics, at the data's own rows.  No marker sits on the torso,
+    so lumbar_extension drives none.  ``markers`` / ``ground_marker``: the
+    few-marker variant the tests use (a marker fixed in ground, tracked
+    against a reference that moves)."""
+    m = gait10dof18musc_model(muscles=muscles)
+    for name, body, loc in markers:
+        m.add_marker(Marker(name, body, loc))
+    data = _load("walk_gait1018_state_reference.json")
+    times = np.asarray(data["time"])
+    ref = synthesize_markers_reference(m, times, data["columns"])
+    if ground_marker:
+        m.add_marker(Marker("lab", "ground", (0.3, 0.1, -0.2)))
+        ref.labels.append("lab")
+        drift = np.stack([0.3 + 0.05 * times, 0.1 + 0.02 * np.sin(times), -0.2 + 0.0 * times], 1)
+        ref.positions = np.concatenate([ref.positions, drift[:, None, :]], 1)
+    m.add_table(ref.flatten())
+    p = MocoProblem(m)
+    p.add_goal(MocoMarkerTrackingGoal("marker_tracking", 1.0, ref))
+    p.add_goal(MocoControlGoal("control_effort", 0.001))
+    p.set_time_bounds(float(times[0]), float(times[-1]))
+    s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals, optim_finite_difference_scheme=fd_scheme,
+                      multibody_dynamics_mode=dynamics)
+    return MocoStudy(p, s)
+
+
+# gait10dof18musc_marker_track_few: pelvis, one femur, the opposite tibia, a
+# foot; the tibia's and the foot's off the body origin
+GAIT_MARKERS_FEW = (
+    ("pelvis_origin", "pelvis", (0.0, 0.0, 0.0)),
+    ("thigh_r", "femur_r", (0.0, 0.0, 0.0)),
+    ("shank_l", "tibia_l", (0.03, -0.2, -0.05)),
+    ("heel_r", "calcn_r", (-0.02, 0.02, 0.0)),
+)
+
+
+def gait10dof18musc_marker_track_few(num_mesh_intervals: int = 3, **kw) -> MocoStudy:
+    """gait10dof18musc_marker_track with four markers (pelvis, femur_r,
+    tibia_l, calcn_r) and one fixed in ground: small enough for N = 2-4, with
+    a coordinate that drives no tracked marker (lumbar_extension)."""
+    return gait10dof18musc_marker_track(num_mesh_intervals, markers=GAIT_MARKERS_FEW, ground_marker=True, **kw)
+
+
 def scale_subject(m: Model, length: float = 1.03, mass: float = 1.05) -> Model:
     """A scaled subject (what OpenSim's ScaleTool produces from a generic
     model, uniformly): every length -- joint frame locations, centers of
@@ -676,6 +812,9 @@ CONFIGS = {
     "gait10dof18musc": gait10dof18musc,
     "gait10dof18musc_inverse": gait10dof18musc_inverse,
     "gait10dof18musc_track": gait10dof18musc_track,
+    "double_pendulum_marker_tracking": double_pendulum_marker_tracking,
+    "gait10dof18musc_marker_track": gait10dof18musc_marker_track,
+    "gait10dof18musc_marker_track_few": gait10dof18musc_marker_track_few,
     "wrapped_pendulum": wrapped_pendulum,
     "rajagopal18_inverse": rajagopal18_inverse,
     "rajagopal80": rajagopal80,

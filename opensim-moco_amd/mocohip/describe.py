@@ -16,7 +16,7 @@ import numpy as np
 from .model import CoordinateActuator, DataTable, DeGrooteFregly2016Muscle
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm, MocoControlBoundConstraint,
                       MocoControlGoal, MocoFinalTimeGoal, MocoFrameDistanceConstraint, MocoInitialActivationGoal,
-                      MocoMarkerFinalGoal,
+                      MocoMarkerFinalGoal, MocoMarkerTrackingGoal,
                       MocoStateTrackingGoal, MocoSumSquaredStateGoal, PiecewiseLinearFunction)
 from .splines import gcv_interpolating_ppoly
 
@@ -160,6 +160,13 @@ def describe(study) -> str:
         elif isinstance(g, MocoMarkerFinalGoal):
             out.append(f"goal marker_final {_s(g.name)} {_d(g.weight)} {_s(g.point_name)} "
                        f"{_ds(g.reference_location)}")
+        elif isinstance(g, MocoMarkerTrackingGoal):
+            # the reference's labels with their weights, by reference index
+            # (the table itself is one of the model's)
+            ref = g.markers_reference
+            out.append(" ".join(["goal", "marker_tracking", _s(g.name), _d(g.weight), _s(ref.name),
+                                 str(int(bool(g.allow_unused_references))), str(len(ref.labels))]
+                                + [f"{_s(k)} {_d(v)}" for k, v in zip(ref.labels, ref.weights())]))
         elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
             out.append(f"goal aux_derivatives {_s(g.name)} {_d(g.weight)}")
         else:

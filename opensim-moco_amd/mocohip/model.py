@@ -448,6 +448,48 @@ class Model:
                 return fr.body, tuple(fr.translation)
         return None
 
+    def marker_locations_in_ground(self, coordinates: Dict[str, float]) -> Dict[str, np.ndarray]:
+        """Every marker's location in ground (by marker path) at the given
+        coordinate values (by coordinate name; a missing one is at its
+        default): the position part of the forward kinematics -- parent pose
+        x joint frames x axis functions -- in NumPy, as 4x4 transforms.  For
+        synthesizing marker data from coordinate trajectories (configs.py);
+        not on the hot path."""
+        from .splines import SimmSpline
+
+        def value(f: Function) -> float:
+            if f.kind == abi.MH_FN_CONSTANT:
+                return f.a
+            q = float(coordinates.get(f.coord, qdefault.get(f.coord, 0.0)))
+            if f.kind == abi.MH_FN_LINEAR:
+                return f.scale * (f.a * q + f.b)
+            return f.scale * float(SimmSpline(f.x, f.y)(q))
+
+        def transform(R=None, p=(0.0, 0.0, 0.0)):
+            X = np.eye(4)
+            if R is not None:
+                X[:3, :3] = R
+            X[:3, 3] = p
+            return X
+
+        qdefault = {c.name: c.default_value for c in self.coordinates()}
+        X_G = {"ground": np.eye(4)}
+        for j in self.tree_order():
+            X_FM = np.eye(4)
+            for ax in j.axes:      # translations first, then the rotations in order
+                if ax.type == abi.MH_AXIS_TRANSLATION:
+                    X_FM = X_FM @ transform(p=value(ax.func) * np.asarray(unit3(ax.dir)))
+            for ax in j.axes:
+                if ax.type == abi.MH_AXIS_ROTATION:
+                    a, t = np.asarray(unit3(ax.dir)), value(ax.func)
+                    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+                    X_FM = X_FM @ transform(np.eye(3) + math.sin(t) * K + (1.0 - math.cos(t)) * (K @ K))
+            X_PF = transform(body_fixed_xyz(j.orient_in_parent), j.loc_in_parent)
+            X_BM = transform(body_fixed_xyz(j.orient_in_child), j.loc_in_child)
+            X_G[j.child] = X_G[j.parent] @ X_PF @ X_FM @ np.linalg.inv(X_BM)
+        return {path: (X_G[mk.body] @ np.append(np.asarray(mk.location, float), 1.0))[:3]
+                for path, mk in self.markers.items()}
+
     # ordering ---------------------------------------------------------------
     def tree_order(self) -> List[Joint]:
         """Joints in Simbody mobilized-body order: breadth-first by tree

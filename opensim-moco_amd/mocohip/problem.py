@@ -108,6 +108,62 @@ class MocoMarkerFinalGoal:
     reference_location: Sequence[float] = (0.0, 0.0, 0.0)
 
 
+@dataclass
+class MarkersReference:
+    """OpenSim::MarkersReference: a table of Vec3 columns labelled by marker
+    name or component path (``positions[row][marker][xyz]`` at ``times``) and
+    a weight per marker, 1.0 unless set (the MarkersReference constructor's
+    default).  ``flatten()`` is TimeSeriesTableVec3::flatten(): the columns
+    <label>_1, <label>_2, <label>_3, splined as GCVSplineSet(table) does
+    (degree 5).  As for a state-tracking reference, the flattened table is a
+    table of the model (Model.add_table) under ``name``."""
+    name: str = "markers_reference"
+    times: Sequence[float] = ()
+    labels: List[str] = field(default_factory=list)
+    positions: Optional[np.ndarray] = None
+    marker_weights: Dict[str, float] = field(default_factory=dict)
+    degree: int = 5
+
+    def set_marker_weight(self, label: str, weight: float):
+        self.marker_weights[label] = float(weight)
+
+    def weights(self) -> List[float]:
+        """The weights by reference index (MarkersReference::getWeights)."""
+        return [float(self.marker_weights.get(n, 1.0)) for n in self.labels]
+
+    def flatten(self) -> DataTable:
+        check_redundant_labels(self.labels)
+        pos = np.asarray(self.positions, float)
+        if pos.shape != (len(self.times), len(self.labels), 3):
+            raise ValueError(f"MarkersReference: positions of shape {pos.shape}, expected "
+                             f"{(len(self.times), len(self.labels), 3)}")
+        cols = {f"{n}_{c + 1}": np.ascontiguousarray(pos[:, i, c])
+                for i, n in enumerate(self.labels) for c in range(3)}
+        return DataTable(self.name, np.asarray(self.times, float), cols, degree=self.degree)
+
+
+def check_redundant_labels(labels):
+    """checkRedundantLabels (MocoUtilities.cpp:635-640)."""
+    srt = sorted(labels)
+    for a, b in zip(srt, srt[1:]):
+        if a == b:
+            raise ValueError(f"Label '{a}' appears more than once.")
+
+
+@dataclass
+class MocoMarkerTrackingGoal:
+    """MocoMarkerTrackingGoal (Moco/Moco/MocoGoal/MocoMarkerTrackingGoal.
+    {h,cpp}): the integral over the phase of sum_m w_m |location in ground of
+    model marker m - reference_m(t)|^2, times the weight.  A reference label
+    names a model marker by component path or, failing that, by its name in
+    the marker set; a label that names none is an error unless
+    ``allow_unused_references`` (initializeOnModelImpl, .cpp:28-83)."""
+    name: str = "marker_tracking"
+    weight: float = 1.0
+    markers_reference: Optional[MarkersReference] = None
+    allow_unused_references: bool = False
+
+
 # ------------------------------------------------- functions of time ----
 @dataclass
 class Constant:
@@ -441,6 +497,12 @@ class ProblemRep:
                 ref = [float(v) for v in g.reference_location]
                 for ci, v in enumerate([float(v) for v in mk.location] + ref):
                     gidx.append(body); gcol.append(ci); gw.append(v)
+            elif isinstance(g, MocoMarkerTrackingGoal):
+                if kin is not None:
+                    raise NotImplementedError("MocoMarkerTrackingGoal with prescribed kinematics "
+                                              "(the coordinates are not NLP states)")
+                gs.kind = abi.MH_GOAL_MARKER_TRACKING
+                self._marker_tracking_terms(model, g, gs, gidx, gcol, gw)
             elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
                 gs.kind = abi.MH_GOAL_AUX_DERIVATIVES
                 naux = sum(1 for m in model.muscles if not m.ignore_tendon_compliance
@@ -688,6 +750,41 @@ class ProblemRep:
                         e.g.lower, e.g.upper = -math.inf, 0.0
                     eqs.append(e)
         return eqs, tables, frame_terms
+
+    def _marker_tracking_terms(self, model: Model, g: "MocoMarkerTrackingGoal", gs, gidx, gcol, gw):
+        """MocoMarkerTrackingGoal::initializeOnModelImpl
+        (MocoMarkerTrackingGoal.cpp:28-83): its checks and messages; four
+        terms per tracked marker (include/mocohip.h MH_GOAL_MARKER_TRACKING),
+        the weights matched by reference index."""
+        ref = g.markers_reference
+        if ref is None:
+            raise ValueError("MocoMarkerTrackingGoal: no markers reference")
+        check_redundant_labels(ref.labels)
+        if ref.name not in self.compiled.table_index:
+            raise ValueError(f"reference table {ref.name} not in model")
+        gs.table = self.compiled.table_index[ref.name]
+        cols = self.compiled.table_columns[ref.name]
+        by_name: Dict[str, object] = {}
+        for mk in model.markers.values():
+            by_name.setdefault(mk.name, mk)    # the first of that name, as the C++ builder
+        weights = ref.weights()
+        for i, label in enumerate(ref.labels):
+            mk = model.markers.get(label)      # a component path ...
+            if mk is None:
+                mk = by_name.get(label)        # ... or a name in the marker set
+            if mk is None:
+                if not g.allow_unused_references:
+                    raise ValueError(f"Marker '{label}' unrecognized by the specified model.")
+                continue
+            if weights[i] < 0:
+                raise ValueError(f"MocoMarkerTrackingGoal: negative weight {weights[i]} of marker '{label}'")
+            body = self.compiled.body_index[mk.body]
+            for c in range(3):
+                col = f"{label}_{c + 1}"
+                if col not in cols:
+                    raise ValueError(f"reference table {ref.name} has no column '{col}'")
+                gidx.append(body); gcol.append(cols.index(col)); gw.append(float(mk.location[c]))
+            gidx.append(body); gcol.append(-1); gw.append(weights[i])
 
     @staticmethod
     def _frame_distance_equations(model: Model, pc: "MocoFrameDistanceConstraint", eqs, frame_terms):

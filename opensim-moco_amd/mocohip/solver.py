@@ -86,6 +86,11 @@ class MocoHipSolver:
     optim_constraint_tolerance: float = -1.0
     optim_hessian_approximation: str = "limited-memory"
     optim_ipopt_print_level: int = -1
+    # Ipopt's limited_memory_max_history (quasi-Newton pairs kept; -1: Ipopt's
+    # default, 6).  Not a MocoCasADiSolver property: where the reference sets
+    # optim_hessian_approximation "exact" (exampleMarkerTracking.cpp:147),
+    # which this path does not offer, a longer memory stands in for it
+    optim_ipopt_limited_memory_max_history: int = -1
     # guess: a MocoTrajectory (or a .sto path, guess_file), resampled onto
     # the transcription grid (CasOCTranscription.cpp:593-597); default the
     # bounds-midpoint guess
@@ -113,6 +118,10 @@ class MocoHipSolver:
         elif self.optim_ipopt_print_level != -1:
             opts["print_level"] = int(self.optim_ipopt_print_level)
         opts["hessian_approximation"] = self.optim_hessian_approximation
+        if self.optim_ipopt_limited_memory_max_history != -1:
+            if self.optim_ipopt_limited_memory_max_history < 0:
+                raise ValueError("optim_ipopt_limited_memory_max_history must be >= 0 or -1")
+            opts["limited_memory_max_history"] = int(self.optim_ipopt_limited_memory_max_history)
         if self.optim_max_iterations != -1:
             opts["max_iter"] = int(self.optim_max_iterations)
         if self.optim_convergence_tolerance != -1:

@@ -23,7 +23,9 @@ Layout (little endian, x86-64 struct layout of include/mocohip.h):
   + targets); from version 8 the initial-guess blob is the whole iterate (n
   doubles, what mh_create reads; mh_driver checks it against
   mh_get_nlp_info_for).  Readers accept versions 4 to 8 (a version-6 tape's
-  rule is mapped to v7's value)."""
+  rule is mapped to v7's value).  Goal kinds travel as data: a
+  MH_GOAL_MARKER_TRACKING goal (kind 7) needs no newer version, as the
+  frame-distance path kinds needed none."""
 from __future__ import annotations
 
 import ctypes as C
