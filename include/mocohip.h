@@ -349,11 +349,63 @@ enum mh_goal_kind {
      * over the coordinates on some tracked marker's ancestor chain; along
      * every other input the integrand does not change and the quotient is
      * exactly 0. */
-    MH_GOAL_MARKER_TRACKING = 7
+    MH_GOAL_MARKER_TRACKING = 7,
+    /* (8 is not assigned: a goal of kind 8 is refused as unknown.) */
+    /* MocoTranslationTrackingGoal (MocoTranslationTrackingGoal.cpp:137-161):
+     * weight * duration * quadrature over every grid point of
+     *     L(t, q) = sum over the tracked frames f, in order, of
+     *               w_f * |p_G(origin of frame f; q) - ref_f(t)|^2
+     * with kind 7's conditions (states required; not with prescribed
+     * kinematics; nq <= 64), term layout (four terms per frame), arithmetic
+     * and gradient: in terms one to three goal_weight = the frame origin's
+     * location in its body (a PhysicalOffsetFrame's translation; zeros for a
+     * body frame) and goal_column = the table's <frame>/position_x / _y / _z
+     * column; term four holds w_f (>= 0). */
+    MH_GOAL_TRANSLATION_TRACKING = 9,
+    /* MocoOrientationTrackingGoal (MocoOrientationTrackingGoal.cpp:169-206):
+     * weight * duration * quadrature over every grid point of
+     *     L(t, q) = sum over the tracked frames f, in order, of w_f * theta_f^2
+     * theta_f = the angle of the rotation between the model frame and the
+     * splined, re-normalised quaternion reference (same conditions as kind 7).
+     * Ten consecutive terms per frame, goal_index = the frame's body in all of
+     * them (-1 = ground).  Terms 0-8: goal_weight = R_BO row-major, the
+     * frame's orientation in its body (identity for a body frame); terms 0-3:
+     * goal_column = the table's <frame>/quaternion_e0 .. _e3 columns, the
+     * other terms -1.  Term 9: goal_weight = w_f (>= 0).  Per frame, each
+     * operation rounded on its own (no fused multiply-add), every 3x3 product
+     * entry summed as (a0 b0 + a1 b1) + a2 b2:
+     *   1. R_GM = R_GB(q) R_BO                 (ground: R_GM = R_BO)
+     *   2. e_i = table column i at t
+     *   3. n = sqrt(((e0 e0 + e1 e1) + e2 e2) + e3 e3), e_i = e_i / n (what the
+     *      SimTK::Quaternion(e0, e1, e2, e3) constructor does)
+     *   4. R_GD from e, with q_ij = e_i e_j:
+     *        ((q00 + q11) - q22) - q33   2 (q12 - q03)               2 (q13 + q02)
+     *        2 (q12 + q03)               ((q00 - q11) + q22) - q33   2 (q23 - q01)
+     *        2 (q13 - q02)               2 (q23 + q01)               ((q00 - q11) - q22) + q33
+     *   5. R_MD = R_GM^T R_GD
+     *   6. s = 0.5 (R21 - R12, R02 - R20, R10 - R01) of R_MD
+     *   7. c = 0.5 (((R00 + R11) + R22) - 1)
+     *   8. theta = atan2(sqrt((s0 s0 + s1 s1) + s2 s2), c), in [0, pi]
+     *   9. L += w_f * (theta * theta)          (from L = 0.0)
+     * The reference takes Simbody's convertRotationToAngleAxis angle, in
+     * (-pi, pi], and squares it: the same quantity.  Its rounding is not
+     * pinned (no Simbody to compare with; atan2's rounding is the math
+     * library's).  The branch-free atan2 form has an absolute error of a few
+     * ulp in theta over the whole range.  theta^2 has a kink at theta = pi.
+     * Gradient of kinds 9 and 10: as kind 7's -- finite-difference quotients of
+     * the whole integrand with k_grad's formulas over t (the t0 / tf entries,
+     * seeds 1 - g and g) and over the coordinates on some tracked frame's
+     * ancestor chain; every other entry keeps its bits.
+     * All goals of kinds 7, 9 and 10 of a problem are evaluated by one kernel
+     * launch per objective or gradient evaluation, each distinct body's pose
+     * once per finite-difference lane.  mh_batch_* evaluates constraints and
+     * their Jacobian only: it accepts contexts with these goals and never
+     * reads them, as for every other goal. */
+    MH_GOAL_ORIENTATION_TRACKING = 10
 };
 typedef struct mh_goal {
     int32_t kind;
-    int32_t table;       /* state / marker tracking: reference table       */
+    int32_t table;       /* state / marker / frame tracking: reference table */
     int32_t term_begin;  /* into mh_problem.goal_index / goal_weight       */
     int32_t term_count;  /* control: #controls weighted; tracking: #states */
     int32_t exponent;    /* control goal exponent (>=2)                    */

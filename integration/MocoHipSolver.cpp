@@ -32,6 +32,9 @@
 #include <OpenSim/Moco/MocoGoal/MocoInitialActivationGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoMarkerFinalGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoMarkerTrackingGoal.h>
+#include <OpenSim/Moco/MocoGoal/MocoOrientationTrackingGoal.h>
+#include <OpenSim/Moco/MocoGoal/MocoTranslationTrackingGoal.h>
+#include <OpenSim/Simulation/StatesTrajectory.h>
 #include <OpenSim/Moco/MocoGoal/MocoStateTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoSumSquaredStateGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoGoal.h>
@@ -516,6 +519,127 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
             // (a redundant label cannot be flattened; make_rep reports it)
             if (std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end())
                 prob.model.add_table(toTable(hg.table, mref.getMarkerTable().flatten(), 5));
+        } else if (dynamic_cast<const MocoTranslationTrackingGoal*>(&g) ||
+                   dynamic_cast<const MocoOrientationTrackingGoal*>(&g)) {
+            // The goals keep their splines and an in-memory reference table
+            // private, so the frame data is computed again from what is
+            // public: the states reference (as initializeOnModelImpl does,
+            // MocoOrientationTrackingGoal.cpp:74-109) or the reference file.
+            // frame_paths follows the documented behaviour (empty: every
+            // column), not the inverted test of the reference's code
+            // (DESIGN.md).  The flattened table -- <path>/position_x|y|z or
+            // <path>/quaternion_e0..3 -- goes in as a model table, splined as
+            // GCVSplineSet(table) does (degree 5); the frames as offset
+            // frames with their orientation; mhb::make_rep runs the checks.
+            const bool orient = dynamic_cast<const MocoOrientationTrackingGoal*>(&g) != nullptr;
+            hg.kind = orient ? mhb::Goal::ORIENTATION_TRACKING : mhb::Goal::TRANSLATION_TRACKING;
+            hg.table = (orient ? "rotation_reference_" : "translation_reference_") + g.getName();
+            const auto& pathsProp = g.getPropertyByName("frame_paths");
+            std::vector<std::string> paths;
+            for (int i = 0; i < pathsProp.size(); ++i) paths.push_back(pathsProp.getValue<std::string>(i));
+            const std::string file = g.getPropertyByName(orient ? "rotation_reference_file"
+                                                                : "translation_reference_file").getValue<std::string>();
+            const auto& statesRef = g.getPropertyByName("states_reference").getValue<TableProcessor>();
+            std::vector<double> times;
+            std::vector<std::vector<SimTK::Rotation>> rotations;   // [row][frame]
+            std::vector<std::vector<SimTK::Vec3>> positions;
+            if (!file.empty()) {
+                auto select = [&](const std::vector<std::string>& labels) {
+                    if (paths.empty()) paths = labels;
+                    std::vector<int> cols;
+                    for (const auto& path : paths) {
+                        auto it = std::find(labels.begin(), labels.end(), path);
+                        OPENSIM_THROW_IF(it == labels.end(), Exception,
+                                "Expected frame_paths to match one of the column labels in the {} reference, but "
+                                "frame path '{}' not found in the reference labels.",
+                                orient ? "rotation" : "translation", path);
+                        cols.push_back((int)(it - labels.begin()));
+                    }
+                    return cols;
+                };
+                if (orient) {
+                    TimeSeriesTable_<SimTK::Rotation> t(file);
+                    const auto cols = select(t.getColumnLabels());
+                    for (int r = 0; r < (int)t.getNumRows(); ++r) {
+                        times.push_back(t.getIndependentColumn()[r]);
+                        rotations.emplace_back();
+                        for (int c : cols) rotations.back().push_back(t.getRowAtIndex(r)[c]);
+                    }
+                } else {
+                    TimeSeriesTableVec3 t(file);
+                    const auto cols = select(t.getColumnLabels());
+                    for (int r = 0; r < (int)t.getNumRows(); ++r) {
+                        times.push_back(t.getIndependentColumn()[r]);
+                        positions.emplace_back();
+                        for (int c : cols) positions.back().push_back(t.getRowAtIndex(r)[c]);
+                    }
+                }
+            } else {
+                OPENSIM_THROW_IF(statesRef.empty(), Exception,
+                        "MocoHipSolver: goal '{}': a reference table set in memory cannot be read back from the goal; "
+                        "give it as a file or as a states reference", g.getName());
+                OPENSIM_THROW_IF(paths.empty(), Exception,
+                        "Expected paths in the frame_paths property, but none were found.");
+                TimeSeriesTable states = statesRef.process("", &model);
+                checkLabelsMatchModelStates(model, states.getColumnLabels());
+                auto traj = StatesTrajectory::createFromStatesStorage(model, convertTableToStorage(states));
+                for (auto state : traj) {
+                    model.realizePosition(state);
+                    times.push_back(state.getTime());
+                    rotations.emplace_back();
+                    positions.emplace_back();
+                    for (const auto& path : paths) {
+                        const Frame& f = model.getComponent<Frame>(path);
+                        rotations.back().push_back(f.getRotationInGround(state));
+                        positions.back().push_back(f.getPositionInGround(state));
+                    }
+                }
+            }
+            const int per = orient ? 4 : 3;
+            std::vector<std::string> labels;
+            static const char* const psfx[3] = {"position_x", "position_y", "position_z"};
+            for (const auto& path : paths)
+                for (int c = 0; c < per; ++c)
+                    labels.push_back(orient ? path + "/quaternion_e" + std::to_string(c) : path + "/" + psfx[c]);
+            TimeSeriesTable flat;
+            std::vector<std::string> sorted(paths);
+            std::sort(sorted.begin(), sorted.end());
+            // (a redundant label cannot be a column twice; make_rep reports it)
+            if (std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end()) {
+                flat.setColumnLabels(labels);
+                for (size_t r = 0; r < times.size(); ++r) {
+                    SimTK::RowVector row((int)labels.size());
+                    for (size_t i = 0; i < paths.size(); ++i) {
+                        if (orient) {
+                            const auto e = rotations[r][i].convertRotationToQuaternion();
+                            for (int c = 0; c < 4; ++c) row[(int)i * 4 + c] = e[c];
+                        } else {
+                            for (int c = 0; c < 3; ++c) row[(int)i * 3 + c] = positions[r][i][c];
+                        }
+                    }
+                    flat.appendRow(times[r], row);
+                }
+                prob.model.add_table(toTable(hg.table, flat, 5));
+            }
+            const auto& ws = g.getPropertyByName(orient ? "rotation_weights" : "translation_weights")
+                                     .getValue<MocoWeightSet>();
+            for (const auto& path : paths) {
+                hg.weights.push_back({path, ws.contains(path) ? ws.get(path).getWeight() : 1.0});
+                if (!model.hasComponent<Frame>(path)) continue;   // make_rep: no frame
+                const Frame& f = model.getComponent<Frame>(path);
+                const Frame& base = f.findBaseFrame();
+                const SimTK::Transform X_BO = f.findTransformInBaseFrame();
+                const SimTK::Vec3 xyz = X_BO.R().convertRotationToBodyFixedXYZ();
+                mhb::OffsetFrame of;
+                of.name = path;
+                of.path = path;
+                of.body = &base == &model.getGround() ? "ground" : base.getName();
+                for (int d = 0; d < 3; ++d) {
+                    of.translation[d] = X_BO.p()[d];
+                    of.orientation[d] = xyz[d];
+                }
+                prob.model.add_offset_frame(of);
+            }
         } else {
             OPENSIM_THROW(Exception, "MocoHipSolver: goal '{}' of type '{}' is not supported (SURVEY §8 A11)",
                     g.getName(), g.getConcreteClassName());

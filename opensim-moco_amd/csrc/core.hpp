@@ -2053,11 +2053,17 @@ __device__ __forceinline__ void gather_inputs(const double* __restrict__ x, cons
     for (int j = L.NS + L.NC + L.NDV + L.NM; j < NI; ++j) in[j] = 0.0;   // slacks: no goal reads them
 }
 
+// Goals that k_marker_tracking evaluates: marker tracking, and the frame
+// tracking goals (translation: position items like markers; orientation).
+__host__ __device__ __forceinline__ bool goal_tracked_items(int kind) {
+    return kind == MH_GOAL_MARKER_TRACKING || kind == MH_GOAL_TRANSLATION_TRACKING ||
+           kind == MH_GOAL_ORIENTATION_TRACKING;
+}
 // Goals with an integral (quadrature of an integrand): all but the endpoint
-// costs (final time, final marker) and the marker-tracking goal, whose
+// costs (final time, final marker) and the marker / frame tracking goals, whose
 // integrand and gradient k_marker_tracking writes into the same slots.
 __host__ __device__ __forceinline__ bool goal_integral(int kind) {
-    return kind != MH_GOAL_FINAL_TIME && kind != MH_GOAL_MARKER_FINAL && kind != MH_GOAL_MARKER_TRACKING;
+    return kind != MH_GOAL_FINAL_TIME && kind != MH_GOAL_MARKER_FINAL && !goal_tracked_items(kind);
 }
 constexpr int MH_MARKER_MAX_Q = 64;   // coordinates a marker goal's kernel holds per lane
 
@@ -2071,24 +2077,29 @@ struct GoalSet {
     const double* gw;
 };
 
-// Marker-tracking goals (MH_GOAL_MARKER_TRACKING) as k_marker_tracking reads
-// them: the markers of all such goals in goal order, goal j's being
-// mbegin[j] .. mbegin[j + 1].  tab has FrameDist's layout (one body per
-// marker where FrameDist has two per equation): [nm] slot of each marker's
-// body (-1: ground), [2 nslots] begin / count of each slot's chain in the body
-// list, [nq] lane index l of each coordinate (-1: on no tracked chain), [nlc]
-// coordinate of lane l, the chains' bodies root first; then [nm] the first of
-// each marker's four terms, [ntg] each goal's index in the GoalSet, [ntg + 1]
-// mbegin, [nlc][nslots] whether lane l's coordinate drives a body of the
-// slot's chain.
+// The tracked items of the marker and frame tracking goals (kinds 7, 9, 10) as
+// k_marker_tracking reads them: a position item per marker or translation
+// frame (four terms, three reference values), an orientation item per
+// orientation frame (ten terms, four reference values); the items of all such
+// goals in goal order, goal j's being mbegin[j] .. mbegin[j + 1].  tab has
+// FrameDist's layout (one body per item where FrameDist has two per
+// equation): [nm] slot of each item's body (-1: ground), [2 nslots] begin /
+// count of each slot's chain in the body list, [nq] lane index l of each
+// coordinate (-1: on no tracked chain), [nlc] coordinate of lane l, the
+// chains' bodies root first; then [nm] the first of each item's terms, [ntg]
+// each goal's index in the GoalSet, [ntg + 1] mbegin, [nlc][nslots] whether
+// lane l's coordinate drives a body of the slot's chain; then [nm] each
+// item's type (0: position, 1: orientation), [nm] the offset of its reference
+// values among a time lane's nref, [nref] the item of each reference value.
 struct MarkerTrack {
     const int* __restrict__ tab;
-    int nm;          // tracked markers (0: no such goal)
-    int ntg;         // marker-tracking goals
-    int nslots;      // distinct bodies that carry a tracked marker
+    int nm;          // tracked items (0: no such goal)
+    int ntg;         // marker / frame tracking goals
+    int nslots;      // distinct bodies that carry a tracked item
     int nlc;         // coordinates with lanes
     int nq;
     int nchain;      // bodies in all chains
+    int nref;        // reference values per time lane (3 or 4 per item)
     __device__ __forceinline__ const int* slot() const { return tab; }
     __device__ __forceinline__ const int* chain() const { return tab + nm; }
     __device__ __forceinline__ const int* lane() const { return tab + nm + 2 * nslots; }
@@ -2098,6 +2109,9 @@ struct MarkerTrack {
     __device__ __forceinline__ const int* goal() const { return term() + nm; }
     __device__ __forceinline__ const int* mbegin() const { return goal() + ntg; }
     __device__ __forceinline__ const int* on_chain() const { return mbegin() + ntg + 1; }
+    __device__ __forceinline__ const int* type() const { return on_chain() + nlc * nslots; }
+    __device__ __forceinline__ const int* roff() const { return type() + nm; }
+    __device__ __forceinline__ const int* ritem() const { return roff() + nm; }
 };
 
 __device__ double goal_integrand(const DevModel& M, const GoalSet& GS, int g, double t,
@@ -2392,7 +2406,7 @@ struct mh_ctx {
     double* d_xch = nullptr;       // k_role -> k_couple exchange [interval][point][NO][3]
     double* d_ep = nullptr;        // endpoint-cost values per goal (k_marker_final)
     bool has_marker = false;
-    // marker-tracking goals (MarkerTrack): the int table as uploaded and the
+    // marker / frame tracking goals (MarkerTrack): the int table as uploaded and the
     // dynamic LDS of k_marker_tracking in objective / gradient mode
     MarkerTrack MT{};
     std::vector<int> mt_tab;

@@ -88,8 +88,11 @@ void Model::add_offset_frame(OffsetFrame f) {
     offset_frames.push_back(std::move(f));
 }
 
-bool Model::find_frame(const std::string& path, std::string& body_name, double location[3]) const {
+bool Model::find_frame(const std::string& path, std::string& body_name, double location[3],
+        double* R_BO) const {
     location[0] = location[1] = location[2] = 0.0;
+    if (R_BO)
+        for (int k = 0; k < 9; ++k) R_BO[k] = k % 4 == 0 ? 1.0 : 0.0;
     if (path == "/ground" || path == "ground") { body_name = "ground"; return true; }
     for (auto& b : bodies)
         if (path == b.name || path == "/bodyset/" + b.name) { body_name = b.name; return true; }
@@ -97,6 +100,7 @@ bool Model::find_frame(const std::string& path, std::string& body_name, double l
         if (path == f.path || path == f.name) {
             body_name = f.body;
             for (int c = 0; c < 3; ++c) location[c] = f.translation[c];
+            if (R_BO) body_fixed_xyz(f.orientation, R_BO);
             return true;
         }
     return false;
@@ -872,6 +876,50 @@ void make_rep(const Problem& P, ProblemRep& R) {
             }
             break;
         }
+        case Goal::TRANSLATION_TRACKING:
+        case Goal::ORIENTATION_TRACKING: {
+            // MocoTranslationTrackingGoal / MocoOrientationTrackingGoal::
+            // initializeOnModelImpl (problem.py _frame_tracking_terms): four
+            // terms per tracked frame (as a marker's), or ten (R_BO, the
+            // quaternion columns, the weight)
+            const bool orient = g.kind == Goal::ORIENTATION_TRACKING;
+            const std::string cls = orient ? "MocoOrientationTrackingGoal" : "MocoTranslationTrackingGoal";
+            if (presc) fail(cls + " with prescribed kinematics (the coordinates are not NLP states)");
+            gs.kind = orient ? MH_GOAL_ORIENTATION_TRACKING : MH_GOAL_TRANSLATION_TRACKING;
+            std::vector<std::string> labels;
+            for (auto& kv : g.weights) labels.push_back(kv.first);
+            std::sort(labels.begin(), labels.end());   // checkRedundantLabels
+            auto dup = std::adjacent_find(labels.begin(), labels.end());
+            if (dup != labels.end()) fail("Label '" + *dup + "' appears more than once.");
+            const int ti = lookup(R.cm.table_index, g.table);
+            if (ti < 0) fail("reference table " + g.table + " not in model");
+            gs.table = R.cm.table_index[ti].second;
+            const auto& cols = R.cm.table_columns[lookup(R.cm.table_columns, g.table)].second;
+            static const char* const psfx[3] = {"position_x", "position_y", "position_z"};
+            static const char* const qsfx[4] = {"quaternion_e0", "quaternion_e1", "quaternion_e2", "quaternion_e3"};
+            for (auto& kv : g.weights) {
+                std::string body_name;
+                double loc[3], R_BO[9];
+                if (!model.find_frame(kv.first, body_name, loc, R_BO))
+                    fail(cls + ": no frame '" + kv.first + "' in the model");
+                if (kv.second < 0)
+                    fail(cls + ": negative weight " + num(kv.second) + " of frame '" + kv.first + "'");
+                const int body = R.cm.index_of_body(body_name);
+                int ci[4] = {-1, -1, -1, -1};
+                for (int c = 0; c < (orient ? 4 : 3); ++c) {
+                    const std::string col = kv.first + "/" + (orient ? qsfx[c] : psfx[c]);
+                    auto it = std::find(cols.begin(), cols.end(), col);
+                    if (it == cols.end()) fail("reference table " + g.table + " has no column '" + col + "'");
+                    ci[c] = (int)(it - cols.begin());
+                }
+                if (orient)
+                    for (int k = 0; k < 9; ++k) term(body, k < 4 ? ci[k] : -1, R_BO[k]);
+                else
+                    for (int c = 0; c < 3; ++c) term(body, ci[c], loc[c]);
+                term(body, -1, kv.second);
+            }
+            break;
+        }
         case Goal::AUX_DERIVATIVES: {
             gs.kind = MH_GOAL_AUX_DERIVATIVES;
             int naux = 0;
@@ -1386,6 +1434,10 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
                 g.kind = Goal::MARKER_TRACKING;
                 g.name = t.s(); g.weight = t.d(); g.table = t.s(); g.allow_unused_references = t.i() != 0;
                 g.weights = read_weights(t);
+            } else if (kind == "translation_tracking" || kind == "orientation_tracking") {
+                g.kind = kind == "translation_tracking" ? Goal::TRANSLATION_TRACKING : Goal::ORIENTATION_TRACKING;
+                g.name = t.s(); g.weight = t.d(); g.table = t.s();
+                g.weights = read_weights(t);
             } else if (kind == "aux_derivatives") {
                 g.kind = Goal::AUX_DERIVATIVES;
                 g.name = t.s(); g.weight = t.d();
@@ -1418,12 +1470,13 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
                 pc.frame_pairs.push_back(fp);
             }
             P.add_path_constraint(pc);
-        } else if (rec == "offsetframe") {
+        } else if (rec == "offsetframe" || rec == "orientedframe") {
             OffsetFrame f;
             f.name = t.s();
             f.body = t.s();
             t.d3(f.translation);
             f.path = t.s();
+            if (rec == "orientedframe") t.d3(f.orientation);
             M.add_offset_frame(f);
         } else if (rec == "parameter") {
             Parameter par;

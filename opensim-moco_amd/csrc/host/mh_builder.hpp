@@ -135,13 +135,14 @@ struct Marker {
     std::string path;
 };
 
-// PhysicalOffsetFrame on a body or ground (model.py OffsetFrame): only the
-// translation is kept; path /bodyset/<body>/<name> (/ground/<name>) unless
-// given.
+// PhysicalOffsetFrame on a body or ground (model.py OffsetFrame): the
+// translation and the orientation (body-fixed XYZ angles); path
+// /bodyset/<body>/<name> (/ground/<name>) unless given.
 struct OffsetFrame {
     std::string name, body;
     double translation[3] = {0, 0, 0};
     std::string path;
+    double orientation[3] = {0, 0, 0};
 };
 
 // A function of time as a piecewise polynomial: breaks[nseg + 1] and
@@ -185,8 +186,10 @@ public:
 
     void add_offset_frame(OffsetFrame f);
     // (body name or "ground", location in that body) of the Frame at path:
-    // /ground, /bodyset/<body>, a body name or a registered offset frame
-    bool find_frame(const std::string& path, std::string& body, double location[3]) const;
+    // /ground, /bodyset/<body>, a body name or a registered offset frame;
+    // R_BO (optional, row-major): the frame's orientation in that body
+    bool find_frame(const std::string& path, std::string& body, double location[3],
+            double* R_BO = nullptr) const;
     void add_body(const Body& b) { bodies.push_back(b); }
     void add_joint(Joint j);
     void add_muscle(Muscle m);
@@ -244,16 +247,19 @@ struct VariableInfo {
 
 struct Goal {
     enum Kind { CONTROL, STATE_TRACKING, FINAL_TIME, SUM_SQUARED_STATE, INITIAL_ACTIVATION, MARKER_FINAL,
-                AUX_DERIVATIVES, MARKER_TRACKING };
+                AUX_DERIVATIVES, MARKER_TRACKING, TRANSLATION_TRACKING, ORIENTATION_TRACKING };
     Kind kind = CONTROL;
     std::string name;
     double weight = 1.0;
     int exponent = 2;
     // control / state weights; marker tracking: the reference's labels with
-    // their weights, by reference index
+    // their weights, by reference index; translation / orientation tracking:
+    // the tracked frame paths with their weights, in order
     std::vector<std::pair<std::string, double>> weights;
     // state tracking reference; marker tracking: the flattened markers table
-    // (columns <label>_1, _2, _3), one of the model's tables
+    // (columns <label>_1, _2, _3), one of the model's tables; translation /
+    // orientation tracking: the flattened frame table (columns
+    // <path>/position_x|y|z or <path>/quaternion_e0..3)
     std::string table;
     bool allow_unused_references = false;                   // marker tracking
     std::string mode = "endpoint_constraint";               // initial activation

@@ -592,8 +592,43 @@ __global__ void __launch_bounds__(128) k_marker_final(DevModel M, Layout L, Goal
     }
 }
 
-// MocoMarkerTrackingGoal (MocoMarkerTrackingGoal.cpp:85-107; include/mocohip.h
-// MH_GOAL_MARKER_TRACKING): block = grid point k, all of them.  mode 0: the
+// The orientation error of one tracked frame (include/mocohip.h
+// MH_GOAL_ORIENTATION_TRACKING, steps 1 to 8, squared): A = the body's pose
+// (null: ground), B = R_BO row-major (nine term weights), e = the four splined
+// quaternion values.
+__device__ __forceinline__ double orientation_error_squared(const double* A, const double* B, const double* e) {
+#pragma clang fp contract(off)
+    double Rm[9];
+    if (A) {
+        for (int i = 0; i < 3; ++i)
+            for (int j = 0; j < 3; ++j)
+                Rm[3 * i + j] = (A[3 * i] * B[j] + A[3 * i + 1] * B[3 + j]) + A[3 * i + 2] * B[6 + j];
+    } else {
+        for (int i = 0; i < 9; ++i) Rm[i] = B[i];
+    }
+    const double n = sqrt(((e[0] * e[0] + e[1] * e[1]) + e[2] * e[2]) + e[3] * e[3]);
+    const double e0 = e[0] / n, e1 = e[1] / n, e2 = e[2] / n, e3 = e[3] / n;
+    const double q00 = e0 * e0, q11 = e1 * e1, q22 = e2 * e2, q33 = e3 * e3;
+    const double q01 = e0 * e1, q02 = e0 * e2, q03 = e0 * e3, q12 = e1 * e2, q13 = e1 * e3, q23 = e2 * e3;
+    const double Rd[9] = {((q00 + q11) - q22) - q33, 2.0 * (q12 - q03), 2.0 * (q13 + q02),
+                          2.0 * (q12 + q03), ((q00 - q11) + q22) - q33, 2.0 * (q23 - q01),
+                          2.0 * (q13 - q02), 2.0 * (q23 + q01), ((q00 - q11) - q22) + q33};
+    double R[9];   // R_MD = R_GM^T R_GD
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j)
+            R[3 * i + j] = (Rm[i] * Rd[j] + Rm[3 + i] * Rd[3 + j]) + Rm[6 + i] * Rd[6 + j];
+    const double s0 = 0.5 * (R[7] - R[5]), s1 = 0.5 * (R[2] - R[6]), s2 = 0.5 * (R[3] - R[1]);
+    const double c = 0.5 * (((R[0] + R[4]) + R[8]) - 1.0);
+    const double th = atan2(sqrt((s0 * s0 + s1 * s1) + s2 * s2), c);
+    return th * th;
+}
+
+// The marker and frame tracking goals (MocoMarkerTrackingGoal.cpp:85-107,
+// MocoTranslationTrackingGoal.cpp:137-161, MocoOrientationTrackingGoal.cpp:
+// 169-206; include/mocohip.h MH_GOAL_MARKER_TRACKING to
+// MH_GOAL_ORIENTATION_TRACKING) over their tracked items: a position item per
+// marker or translation frame, an orientation item per orientation frame.
+// Block = grid point k, all of them.  mode 0: the
 // integrand, C[k * ngoals + gi] = quad[k] * L.  mode 1 (gradient) also the
 // finite-difference quotients of the whole integrand with k_grad's formulas
 // and arithmetic, added to what k_grad left in grad's coordinate entries of
@@ -605,11 +640,12 @@ __global__ void __launch_bounds__(128) k_marker_final(DevModel M, Layout L, Goal
 // Phase 1: the pose of each distinct body at lane 0 and at every coordinate
 // lane whose coordinate is on the body's chain (MarkerTrack::on_chain; LDS, 12
 // doubles), and the
-// reference of every marker at the base and the time lanes' times.
-// Phase 2: thread = (lane, marker): the squared distance, from the lane's
-// pose where phase 1 wrote one and lane 0's otherwise -- a marker off the
-// perturbed chain gives both sides of the quotient the same bits.
-// Phase 3: thread = (lane, goal) sums the goal's markers in order; then
+// reference of every item (three positions or four quaternion values) at the
+// base and the time lanes' times.
+// Phase 2: thread = (lane, item): the squared distance or squared angle, from
+// the lane's pose where phase 1 wrote one and lane 0's otherwise -- an item
+// off the perturbed chain gives both sides of the quotient the same bits.
+// Phase 3: thread = (lane, goal) sums the goal's items in order; then
 // thread = direction forms the quotients.
 __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, GoalSet GS, MarkerTrack T, int fd,
         double h, int mode, const double* __restrict__ x, const double* __restrict__ grid,
@@ -618,14 +654,14 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
 #pragma clang fp contract(off)
     extern __shared__ double mt_lds[];
     const int k = blockIdx.x;
-    const int ns = T.nslots, nm = T.nm, nlc = T.nlc, ntg = T.ntg;
+    const int ns = T.nslots, nm = T.nm, nlc = T.nlc, ntg = T.ntg, nref = T.nref;
     const int sides = fd == MH_FD_CENTRAL ? 2 : 1;
     const int npl = 1 + (mode ? sides * nlc : 0);   // lanes with poses of their own
     const int nt = mode ? 2 * sides : 0;            // time lanes
     const int nl = npl + nt;
     double* pose = mt_lds;                          // [npl][slot][12]
-    double* ref = pose + (long)npl * ns * 12;       // [1 + nt][marker][3]
-    double* sq = ref + (long)(1 + nt) * nm * 3;     // [lane][marker]
+    double* ref = pose + (long)npl * ns * 12;       // [1 + nt][nref]: item m's from roff[m]
+    double* sq = ref + (long)(1 + nt) * nref;       // [lane][item]
     double* Lv = sq + (long)nl * nm;                // [lane][goal]
     const double g = grid[k], dur = x[1] - x[0], t = dur * g + x[0];
     const double* q = x + 2 + (long)k * L.NS;
@@ -646,15 +682,15 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
         for (int i = 0; i < 9; ++i) o[i] = R[i];
         for (int i = 0; i < 3; ++i) o[9 + i] = p[i];
     }
-    for (int w = threadIdx.x; w < (1 + nt) * nm * 3; w += blockDim.x) {
-        const int tl = w / (3 * nm), r = w - tl * 3 * nm, m = r / 3, c = r - 3 * m;
+    for (int w = threadIdx.x; w < (1 + nt) * nref; w += blockDim.x) {
+        const int tl = w / nref, r = w - tl * nref, m = T.ritem()[r], c = r - T.roff()[m];
         double tt = t;
         if (tl > 0) {
             const int d = (tl - 1) & 1;
             const double seed = d == 0 ? 1.0 - g : g;
             tt = fd == MH_FD_BACKWARD || tl - 1 >= 2 ? t - h * seed : t + h * seed;
         }
-        // the goal of marker m: the one whose marker range holds it
+        // the goal of item m: the one whose item range holds it
         int j = 0;
         while (j + 1 < ntg && T.mbegin()[j + 1] <= m) ++j;
         ref[w] = table_eval(M, GS.goals[T.goal()[j]].table, GS.gcol[T.term()[m] + c], tt);
@@ -665,6 +701,16 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
         const int tl = ln < npl ? 0 : ln - npl + 1;
         const int sl = T.slot()[m];
         const double* w3 = GS.gw + T.term()[m];
+        if (T.type()[m]) {   // orientation: R_BO in w3[0..9), four reference values
+            const double* A = nullptr;
+            if (sl >= 0) {
+                int pl = ln < npl ? ln : 0;
+                if (pl > 0 && !T.on_chain()[(pl - 1) % nlc * ns + sl]) pl = 0;
+                A = pose + ((long)pl * ns + sl) * 12;
+            }
+            sq[w] = orientation_error_squared(A, w3, ref + (long)tl * nref + T.roff()[m]);
+            continue;
+        }
         double p0 = w3[0], p1 = w3[1], p2 = w3[2];
         if (sl >= 0) {
             int pl = ln < npl ? ln : 0;
@@ -674,7 +720,7 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
             p1 = A[10] + ((A[3] * w3[0] + A[4] * w3[1]) + A[5] * w3[2]);
             p2 = A[11] + ((A[6] * w3[0] + A[7] * w3[1]) + A[8] * w3[2]);
         }
-        const double* rf = ref + ((long)tl * nm + m) * 3;
+        const double* rf = ref + (long)tl * nref + T.roff()[m];
         const double d0 = p0 - rf[0], d1 = p1 - rf[1], d2 = p2 - rf[2];
         sq[w] = (d0 * d0 + d1 * d1) + d2 * d2;
     }
@@ -682,7 +728,8 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
     for (int w = threadIdx.x; w < nl * ntg; w += blockDim.x) {
         const int ln = w / ntg, j = w - ln * ntg;
         double s = 0.0;
-        for (int m = T.mbegin()[j]; m < T.mbegin()[j + 1]; ++m) s += GS.gw[T.term()[m] + 3] * sq[(long)ln * nm + m];
+        for (int m = T.mbegin()[j]; m < T.mbegin()[j + 1]; ++m)
+            s += GS.gw[T.term()[m] + (T.type()[m] ? 9 : 3)] * sq[(long)ln * nm + m];
         Lv[w] = s;
     }
     __syncthreads();
@@ -1675,12 +1722,15 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
     // (a bad index would be an out-of-bounds device read)
     for (int g = 0; g < p->ngoals; ++g) {
         const mh_goal& G = p->goals[g];
-        const bool tracking = G.kind == MH_GOAL_MARKER_TRACKING;
+        // tracked items (kinds 7, 9, 10): tn terms each, the last one the weight
+        const bool tracking = goal_tracked_items(G.kind);
+        const int tn = G.kind == MH_GOAL_ORIENTATION_TRACKING ? 10 : 4;
+        const int tcols = G.kind == MH_GOAL_ORIENTATION_TRACKING ? 4 : 3;   // leading terms with a column
         const bool marker = G.kind == MH_GOAL_MARKER_FINAL || tracking;
         if (G.kind < MH_GOAL_CONTROL || (G.kind > MH_GOAL_MARKER_FINAL && !tracking))
             return set_err(MH_ERR_INVALID, "goal %d: unknown kind %d", g, G.kind);
         if (G.term_begin < 0 || G.term_count < 0 || (int64_t)G.term_begin + G.term_count > p->nterms ||
-                (G.kind == MH_GOAL_MARKER_FINAL && G.term_count != 6) || (tracking && G.term_count % 4 != 0))
+                (G.kind == MH_GOAL_MARKER_FINAL && G.term_count != 6) || (tracking && G.term_count % tn != 0))
             return set_err(MH_ERR_INVALID, "goal %d: bad terms", g);
         if ((G.kind == MH_GOAL_STATE_TRACKING || tracking) && (G.table < 0 || G.table >= M.ntables))
             return set_err(MH_ERR_INVALID, "goal %d: bad table", g);
@@ -1694,17 +1744,19 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
             case MH_GOAL_CONTROL: hi = c->NC; break;
             case MH_GOAL_STATE_TRACKING: case MH_GOAL_SUM_SQUARED_STATE: hi = c->NS; break;
             case MH_GOAL_AUX_DERIVATIVES: hi = c->NAR; break;
-            case MH_GOAL_MARKER_FINAL: case MH_GOAL_MARKER_TRACKING: hi = M.nbodies; break;
+            case MH_GOAL_MARKER_FINAL: case MH_GOAL_MARKER_TRACKING: case MH_GOAL_TRANSLATION_TRACKING:
+            case MH_GOAL_ORIENTATION_TRACKING: hi = M.nbodies; break;
             default: hi = INT32_MAX; break;   // final time: no terms read
             }
             if (idx < (marker ? -1 : 0) || idx >= hi)
                 return set_err(MH_ERR_INVALID, "goal %d: term %d index %d out of range", g, k, idx);
-            const bool column = G.kind == MH_GOAL_STATE_TRACKING || (tracking && (k - G.term_begin) % 4 != 3);
+            const int ti = tracking ? (k - G.term_begin) % tn : 0;   // the term within its item
+            const bool column = G.kind == MH_GOAL_STATE_TRACKING || (tracking && ti < tcols);
             if (column && (p->goal_column[k] < 0 || p->goal_column[k] >= M.tables[G.table].ncol))
                 return set_err(MH_ERR_INVALID, "goal %d: term %d column out of range", g, k);
-            if (tracking && (k - G.term_begin) % 4 == 3 && !(p->goal_weight[k] >= 0.0))
+            if (tracking && ti == tn - 1 && !(p->goal_weight[k] >= 0.0))
                 return set_err(MH_ERR_INVALID, "goal %d: term %d: negative marker weight", g, k);
-            if (tracking && idx != p->goal_index[k - (k - G.term_begin) % 4])
+            if (tracking && idx != p->goal_index[k - ti])
                 return set_err(MH_ERR_INVALID, "goal %d: term %d: a marker's terms name different bodies", g, k);
         }
     }
@@ -1936,18 +1988,22 @@ static FrameDist frame_distance_tables(mh_ctx* c, const mh_model& M, const std::
     return F;
 }
 
-// MarkerTrack's int table (core.hpp) and counts for the marker-tracking goals
-// of c->goals, and k_marker_tracking's LDS in both modes (its layout).
+// MarkerTrack's int table (core.hpp) and counts for the marker and frame
+// tracking goals of c->goals, and k_marker_tracking's LDS in both modes (its layout).
 static MarkerTrack marker_tracking_tables(mh_ctx* c, const mh_model& M, const std::vector<int>& coord_body) {
     MarkerTrack T{};
-    std::vector<int> ref_body, term, goal, mbegin;
+    std::vector<int> ref_body, term, goal, mbegin, type, roff, ritem;
     for (size_t g = 0; g < c->goals.size(); ++g) {
         const mh_goal& G = c->goals[g];
-        if (G.kind != MH_GOAL_MARKER_TRACKING) continue;
+        if (!goal_tracked_items(G.kind)) continue;
+        const bool orient = G.kind == MH_GOAL_ORIENTATION_TRACKING;
         goal.push_back((int)g);
         mbegin.push_back((int)term.size());
-        for (int k = G.term_begin; k < G.term_begin + G.term_count; k += 4) {
+        for (int k = G.term_begin; k < G.term_begin + G.term_count; k += orient ? 10 : 4) {
             ref_body.push_back(c->gidx[k]);
+            type.push_back(orient);
+            roff.push_back((int)ritem.size());
+            ritem.insert(ritem.end(), orient ? 4 : 3, (int)term.size());
             term.push_back(k);
         }
     }
@@ -1960,6 +2016,7 @@ static MarkerTrack marker_tracking_tables(mh_ctx* c, const mh_model& M, const st
     T.nlc = B.nlc;
     T.nq = M.nq;
     T.nchain = B.nchain;
+    T.nref = (int)ritem.size();
     c->mt_tab = B.tab;
     c->mt_tab.insert(c->mt_tab.end(), term.begin(), term.end());
     c->mt_tab.insert(c->mt_tab.end(), goal.begin(), goal.end());
@@ -1974,12 +2031,29 @@ static MarkerTrack marker_tracking_tables(mh_ctx* c, const mh_model& M, const st
             const int* cb = bodies + chain[2 * sl];
             c->mt_tab.push_back(std::find(cb, cb + chain[2 * sl + 1], coord_body[coord[l]]) != cb + chain[2 * sl + 1]);
         }
+    c->mt_tab.insert(c->mt_tab.end(), type.begin(), type.end());
+    c->mt_tab.insert(c->mt_tab.end(), roff.begin(), roff.end());
+    c->mt_tab.insert(c->mt_tab.end(), ritem.begin(), ritem.end());
     const size_t sides = c->fd == MH_FD_CENTRAL ? 2 : 1;
     for (int mode = 0; mode < 2; ++mode) {
         const size_t npl = 1 + (mode ? sides * T.nlc : 0), nt = mode ? 2 * sides : 0, nl = npl + nt;
-        c->mt_lds[mode] = sizeof(double) * (12 * npl * T.nslots + 3 * (1 + nt) * T.nm + nl * T.nm + nl * T.ntg);
+        c->mt_lds[mode] = sizeof(double) * (12 * npl * T.nslots + (1 + nt) * T.nref + nl * T.nm + nl * T.ntg);
     }
     return T;
+}
+
+// The kinematics kernels' tables, and their LDS bounds (host only: mh_create
+// and the layout query refuse the same problems).
+static int kinematics_tables(mh_ctx* c, const mh_model& M, const std::vector<int>& coord_body, FrameDist& FD,
+        MarkerTrack& MT) {
+    FD = frame_distance_tables(c, M, coord_body);
+    if (c->fd_lds > 64 * 1024)
+        return set_err(MH_ERR_UNSUPPORTED, "frame distance: %d bodies x %d lanes exceed the LDS", FD.nslots, FD.nl);
+    MT = marker_tracking_tables(c, M, coord_body);
+    if (c->mt_lds[1] > 64 * 1024)
+        return set_err(MH_ERR_UNSUPPORTED, "marker tracking: %d tracked items on %d bodies x %d coordinate lanes "
+                       "exceed the LDS", MT.nm, MT.nslots, MT.nlc);
+    return MH_OK;
 }
 
 extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out) {
@@ -2029,13 +2103,9 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
         d[5] = std::exp(4.0) - d[4];
     }
 
-    FrameDist FD = frame_distance_tables(c.get(), M, coord_body);
-    if (c->fd_lds > 64 * 1024)
-        return set_err(MH_ERR_UNSUPPORTED, "frame distance: %d bodies x %d lanes exceed the LDS", FD.nslots, FD.nl);
-    MarkerTrack MT = marker_tracking_tables(c.get(), M, coord_body);
-    if (c->mt_lds[1] > 64 * 1024)
-        return set_err(MH_ERR_UNSUPPORTED, "marker tracking: %d markers on %d bodies x %d coordinate lanes exceed "
-                       "the LDS", MT.nm, MT.nslots, MT.nlc);
+    FrameDist FD;
+    MarkerTrack MT;
+    if ((rc = kinematics_tables(c.get(), M, coord_body, FD, MT))) return rc;
     Arena A;
     const size_t o_fdtab = A.put(c->fd_tab.data(), c->fd_tab.size());
     const size_t o_mttab = A.put(c->mt_tab.data(), c->mt_tab.size());
@@ -3819,6 +3889,9 @@ extern "C" int mh_get_nlp_info_for(const mh_problem* p, const mh_options* o, mh_
     int rc = validate_and_layout(c.get(), p, o, coord_body, act_state, ftn_state, mus_control, tau_act,
             tau_deact);
     if (rc) return rc;
+    FrameDist FD;
+    MarkerTrack MT;
+    if ((rc = kinematics_tables(c.get(), p->model, coord_body, FD, MT))) return rc;
     return mh_get_nlp_info(c.get(), info);
 }
 

@@ -8,5 +8,6 @@ from .model import (Axis, Body, Coordinate, CoordinateActuator, DataTable,  # no
                     DeGrooteFregly2016Muscle, ExternalForce, Function, Joint,
                     Model, PathPoint)
 from .problem import (MocoBounds, MocoControlGoal, MocoFinalTimeGoal,  # noqa: F401
-                      MocoProblem, MocoStateTrackingGoal, MocoSumSquaredStateGoal)
+                      MocoOrientationTrackingGoal, MocoProblem, MocoStateTrackingGoal,
+                      MocoSumSquaredStateGoal, MocoTranslationTrackingGoal)
 from .solver import HipNLP, MocoHipSolver, MocoStudy  # noqa: F401

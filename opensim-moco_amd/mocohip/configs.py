@@ -28,8 +28,9 @@ from .osim import add_reserves
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm,
                       MocoControlBoundConstraint, MocoControlGoal, MocoFrameDistanceConstraint,
                       MocoInitialActivationGoal,
-                      MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoMarkerTrackingGoal, MarkersReference,
-                      MocoProblem, MocoStateTrackingGoal, PiecewiseLinearFunction)
+                      FrameReference, MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoMarkerTrackingGoal,
+                      MarkersReference, MocoOrientationTrackingGoal, MocoProblem, MocoStateTrackingGoal,
+                      MocoTranslationTrackingGoal, PiecewiseLinearFunction)
 from .solver import MocoHipSolver, MocoStudy
 
 DATA = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data")
@@ -548,6 +549,152 @@ def gait10dof18musc_marker_track_few(num_mesh_intervals: int = 3, **kw) -> MocoS
     return gait10dof18musc_marker_track(num_mesh_intervals, markers=GAIT_MARKERS_FEW, ground_marker=True, **kw)
 
 
+def double_pendulum_effort(num_mesh_intervals: int = 20, scheme: str = "hermite-simpson",
+                           effort_weight: float = 1.0) -> MocoStudy:
+    """testMocoGoals.cpp:209-232 (setupMocoStudyDoublePendulumMinimizeEffort):
+    ModelFactory::createNLinkPendulum(2), a MocoControlGoal "effort", time [0,
+    2], controls in [-100, 100], q0 from 0 to pi / 2, q1 from pi to 0, speeds
+    in [-50, 50] from 0 to 0, 20 mesh intervals, convergence tolerance 1e-5,
+    explicit dynamics."""
+    m = n_link_pendulum(2)
+    p = MocoProblem(m)
+    p.add_goal(MocoControlGoal("effort", effort_weight))
+    p.set_time_bounds(0, 2)
+    p.set_control_info("/tau0", (-100, 100))
+    p.set_control_info("/tau1", (-100, 100))
+    p.set_state_info("/jointset/j0/q0/value", (-10, 10), 0, math.pi / 2)
+    p.set_state_info("/jointset/j0/q0/speed", (-50, 50), 0, 0)
+    p.set_state_info("/jointset/j1/q1/value", (-10, 10), math.pi, 0)
+    p.set_state_info("/jointset/j1/q1/speed", (-50, 50), 0, 0)
+    s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals, transcription_scheme=scheme,
+                      optim_convergence_tolerance=1e-5, multibody_dynamics_mode="explicit")
+    return MocoStudy(p, s)
+
+
+def states_table(trajectory, name: str = "states_reference") -> DataTable:
+    """MocoTrajectory::exportToStatesTable: the states by path."""
+    return DataTable(name, np.asarray(trajectory.time, float),
+                     {n: np.ascontiguousarray(trajectory.states[:, i]) for i, n in enumerate(trajectory.state_names)})
+
+
+def double_pendulum_swing_states(num_rows: int = 41) -> DataTable:
+    """A smooth stand-in for the effort solution where none has been solved
+    (tests of the lowering and of the kernel): q0 from 0 to pi / 2 and q1 from
+    pi to 0 over [0, 2] along s(t) = (1 - cos(pi t / 2)) / 2, with the speeds
+    that go with it."""
+    t = np.linspace(0.0, 2.0, num_rows)
+    sm, ds = 0.5 * (1.0 - np.cos(0.5 * math.pi * t)), 0.25 * math.pi * np.sin(0.5 * math.pi * t)
+    return DataTable("states_reference", t, {
+        "/jointset/j0/q0/value": 0.5 * math.pi * sm, "/jointset/j0/q0/speed": 0.5 * math.pi * ds,
+        "/jointset/j1/q1/value": math.pi * (1.0 - sm), "/jointset/j1/q1/speed": -math.pi * ds})
+
+
+def double_pendulum_frame_tracking(kind: str = "orientation", reference_solution=None,
+                                   num_mesh_intervals: int = 20, scheme: str = "hermite-simpson",
+                                   fd_scheme: str = "central") -> MocoStudy:
+    """testMocoGoals.cpp:234-256 (testDoublePendulumTracking): the effort
+    problem with the effort goal's weight 0.001 and a tracking goal "tracking"
+    of ``kind`` ("translation" / "orientation") on the frames /bodyset/b0 and
+    /bodyset/b1, its states reference the effort solution (a MocoTrajectory or
+    a states DataTable; None: double_pendulum_swing_states)."""
+    st = double_pendulum_effort(num_mesh_intervals, scheme, effort_weight=0.001)
+    st.solver.optim_finite_difference_scheme = fd_scheme
+    if reference_solution is None:
+        reference_solution = double_pendulum_swing_states()
+    elif not isinstance(reference_solution, DataTable):
+        reference_solution = states_table(reference_solution)
+    cls = {"translation": MocoTranslationTrackingGoal, "orientation": MocoOrientationTrackingGoal}[kind]
+    g = cls("tracking", 1.0, states_reference=reference_solution, frame_paths=["/bodyset/b0", "/bodyset/b1"])
+    st.problem.model.add_table(g.reference_table(st.problem.model))
+    st.problem.add_goal(g)
+    return st
+
+
+def gimbal_motion(times):
+    """A smooth 3-D motion of the gimbal's (qx, qy, qz), within its +-pi / 3."""
+    t = np.asarray(times, float)
+    return {"qx": 0.6 * np.sin(2.0 * t + 0.3), "qy": 0.7 * np.cos(3.0 * t), "qz": -0.5 + 0.8 * t}
+
+
+def gimbal_frame_tracking(num_mesh_intervals: int = 2, scheme: str = "hermite-simpson",
+                          fd_scheme: str = "central") -> MocoStudy:
+    """gimbal_frame_distance's model (a body on a GimbalJoint) with a rotated
+    offset frame "sensor" on the body (translation (-0.5, 0.1, 0.2),
+    orientation (0.4, -0.7, 1.1)): orientation tracking of the sensor (weight
+    2) and of the body frame, translation tracking of the sensor (weight 3),
+    the references given as tables computed along gimbal_motion at 26 rows,
+    plus a control-effort goal (0.001)."""
+    m = gimbal_frame_distance(num_mesh_intervals).problem.model
+    m.add_offset_frame("sensor", "body", (-0.5, 0.1, 0.2), (0.4, -0.7, 1.1))
+    sensor = "/bodyset/body/sensor"
+    times = np.linspace(0.0, 0.5, 26)
+    mot = gimbal_motion(times)
+    poses = [[m.frame_pose_in_ground(f, {n: v[r] for n, v in mot.items()}) for f in (sensor, "/bodyset/body")]
+             for r in range(len(times))]
+    rot = FrameReference(times, [sensor, "/bodyset/body"], np.array([[ps[1] for ps in row] for row in poses]))
+    pos = FrameReference(times, [sensor, "/bodyset/body"], np.array([[ps[0] for ps in row] for row in poses]))
+    go = MocoOrientationTrackingGoal("orientation_tracking", 1.0, reference=rot, frame_weights={sensor: 2.0})
+    gt = MocoTranslationTrackingGoal("translation_tracking", 0.5, reference=pos, frame_paths=[sensor],
+                                     frame_weights={sensor: 3.0})
+    p = MocoProblem(m)
+    p.set_time_bounds(0, 0.5)
+    third = math.pi / 3
+    for n in ("qx", "qy", "qz"):
+        p.set_state_info(f"/jointset/gimbal/{n}/value", (-third, third))
+        p.set_state_info(f"/jointset/gimbal/{n}/speed", (-10, 10))
+    for g in (go, gt):
+        m.add_table(g.reference_table(m))
+        p.add_goal(g)
+    p.add_goal(MocoControlGoal("control_effort", 0.001))
+    s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals, transcription_scheme=scheme,
+                      optim_finite_difference_scheme=fd_scheme)
+    return MocoStudy(p, s)
+
+
+GAIT_ORIENTATION_FRAMES_FEW = ("/bodyset/pelvis", "/bodyset/femur_r", "/bodyset/femur_l", "/bodyset/tibia_r",
+                               "/bodyset/tibia_l")
+# gait10dof18musc_frame_track: the five above, and a sensor frame on each foot
+GAIT_ORIENTATION_FRAMES = GAIT_ORIENTATION_FRAMES_FEW + ("/bodyset/calcn_r/imu_r", "/bodyset/calcn_l/imu_l")
+
+
+def gait10dof18musc_frame_track(num_mesh_intervals: int = 200, markers=GAIT_MARKERS,
+                                frames=GAIT_ORIENTATION_FRAMES, translation: bool = False,
+                                **kw) -> MocoStudy:
+    """gait10dof18musc_marker_track plus a MocoOrientationTrackingGoal
+    "orientation_tracking" (weight 1, frame weights 1) on ``frames`` -- the
+    segments an inertial-sensor set covers; the foot sensors are offset frames
+    rotated in their bodies -- and, with ``translation``, a
+    MocoTranslationTrackingGoal of the pelvis; the states reference is the
+    bundled walking coordinate data, so the references are the frames' poses
+    by forward kinematics at the data's rows.  Markers, segment orientations
+    and the pelvis position share one kernel launch."""
+    st = gait10dof18musc_marker_track(num_mesh_intervals, markers=markers, **kw)
+    m = st.problem.model
+    m.add_offset_frame("imu_r", "calcn_r", (0.1, 0.03, 0.0), (0.1, -0.2, 1.3))
+    m.add_offset_frame("imu_l", "calcn_l", (0.1, 0.03, 0.0), (-0.1, 0.2, 1.3))
+    data = _load("walk_gait1018_state_reference.json")
+    states = DataTable("states_reference", np.asarray(data["time"]),
+                       {k: np.asarray(v, float) for k, v in data["columns"].items()})
+    goals = [MocoOrientationTrackingGoal("orientation_tracking", 1.0, states_reference=states,
+                                         frame_paths=list(frames))]
+    if translation:
+        goals.append(MocoTranslationTrackingGoal("translation_tracking", 1.0, states_reference=states,
+                                                 frame_paths=["/bodyset/pelvis"]))
+    for g in goals:
+        m.add_table(g.reference_table(m))
+    st.problem.goals[1:1] = goals   # after the marker goal, before the effort goal
+    return st
+
+
+def gait10dof18musc_frame_track_few(num_mesh_intervals: int = 3, **kw) -> MocoStudy:
+    """N = 3: orientation tracking of the pelvis, both femurs and both tibias,
+    translation tracking of the pelvis, and a marker goal with two markers
+    (pelvis, tibia_l off the body origin) -- all three item types in one
+    launch."""
+    return gait10dof18musc_frame_track(num_mesh_intervals, markers=(GAIT_MARKERS_FEW[0], GAIT_MARKERS_FEW[2]),
+                                       frames=GAIT_ORIENTATION_FRAMES_FEW, translation=True, **kw)
+
+
 def scale_subject(m: Model, length: float = 1.03, mass: float = 1.05) -> Model:
     """A scaled subject (what OpenSim's ScaleTool produces from a generic
     model, uniformly): every length -- joint frame locations, centers of
@@ -815,6 +962,11 @@ CONFIGS = {
     "double_pendulum_marker_tracking": double_pendulum_marker_tracking,
     "gait10dof18musc_marker_track": gait10dof18musc_marker_track,
     "gait10dof18musc_marker_track_few": gait10dof18musc_marker_track_few,
+    "double_pendulum_effort": double_pendulum_effort,
+    "double_pendulum_frame_tracking": double_pendulum_frame_tracking,
+    "gimbal_frame_tracking": gimbal_frame_tracking,
+    "gait10dof18musc_frame_track": gait10dof18musc_frame_track,
+    "gait10dof18musc_frame_track_few": gait10dof18musc_frame_track_few,
     "wrapped_pendulum": wrapped_pendulum,
     "rajagopal18_inverse": rajagopal18_inverse,
     "rajagopal80": rajagopal80,

@@ -16,7 +16,8 @@ import numpy as np
 from .model import CoordinateActuator, DataTable, DeGrooteFregly2016Muscle
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm, MocoControlBoundConstraint,
                       MocoControlGoal, MocoFinalTimeGoal, MocoFrameDistanceConstraint, MocoInitialActivationGoal,
-                      MocoMarkerFinalGoal, MocoMarkerTrackingGoal,
+                      MocoMarkerFinalGoal, MocoMarkerTrackingGoal, MocoOrientationTrackingGoal,
+                      MocoTranslationTrackingGoal,
                       MocoStateTrackingGoal, MocoSumSquaredStateGoal, PiecewiseLinearFunction)
 from .splines import gcv_interpolating_ppoly
 
@@ -124,6 +125,11 @@ def describe(study) -> str:
     for mk in m.markers.values():
         out.append(f"marker {_s(mk.name)} {_s(mk.body)} {_ds(mk.location)} {_s(mk.path)}")
     for fr in m.offset_frames.values():
+        # (the orientation travels only when there is one: earlier descriptions keep their bytes)
+        if fr.oriented():
+            out.append(f"orientedframe {_s(fr.name)} {_s(fr.body)} {_ds(fr.translation)} {_s(fr.path)} "
+                       f"{_ds(fr.orientation)}")
+            continue
         out.append(f"offsetframe {_s(fr.name)} {_s(fr.body)} {_ds(fr.translation)} {_s(fr.path)}")
     for k in m.constraints:
         out.append(f"constraint {_s(k.name)} {_s(k.dependent)} {_fn(k.function)} {_d(k.scale_factor)}")
@@ -167,6 +173,14 @@ def describe(study) -> str:
             out.append(" ".join(["goal", "marker_tracking", _s(g.name), _d(g.weight), _s(ref.name),
                                  str(int(bool(g.allow_unused_references))), str(len(ref.labels))]
                                 + [f"{_s(k)} {_d(v)}" for k, v in zip(ref.labels, ref.weights())]))
+        elif isinstance(g, (MocoTranslationTrackingGoal, MocoOrientationTrackingGoal)):
+            # the tracked frames (frame_paths applied to the reference's
+            # labels) with their weights; the flattened table is one of the
+            # model's
+            kind = "translation_tracking" if isinstance(g, MocoTranslationTrackingGoal) else "orientation_tracking"
+            paths = g.tracked_frame_paths()
+            out.append(" ".join(["goal", kind, _s(g.name), _d(g.weight), _s(g.reference_name()), str(len(paths))]
+                                + [f"{_s(k)} {_d(g.weight_for_frame(k))}" for k in paths]))
         elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
             out.append(f"goal aux_derivatives {_s(g.name)} {_d(g.weight)}")
         else:

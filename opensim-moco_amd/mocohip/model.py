@@ -291,12 +291,17 @@ class Marker:
 @dataclass
 class OffsetFrame:
     """OpenSim::PhysicalOffsetFrame on a body (or ground); path
-    /bodyset/<body>/<name> (/ground/<name>).  Only the translation is kept:
-    it is all the frame's position in ground needs."""
+    /bodyset/<body>/<name> (/ground/<name>): the translation, and the
+    orientation as body-fixed XYZ angles (PhysicalOffsetFrame's
+    ``orientation``; zeros unless given, and then not serialised)."""
     name: str
     body: str                # body name or "ground"
     translation: Sequence[float] = (0.0, 0.0, 0.0)
     path: str = ""
+    orientation: Sequence[float] = (0.0, 0.0, 0.0)
+
+    def oriented(self) -> bool:
+        return any(float(v) != 0.0 for v in self.orientation)
 
 
 @dataclass
@@ -426,11 +431,13 @@ class Model:
         self.markers[mk.path] = mk
         return mk
 
-    def add_offset_frame(self, name: str, body: str, translation=(0.0, 0.0, 0.0)) -> OffsetFrame:
+    def add_offset_frame(self, name: str, body: str, translation=(0.0, 0.0, 0.0),
+                         orientation=(0.0, 0.0, 0.0)) -> OffsetFrame:
         if body != "ground" and body not in self.bodies:
             raise ValueError(f"offset frame '{name}': no body '{body}'")
         path = f"/ground/{name}" if body == "ground" else f"/bodyset/{body}/{name}"
-        fr = OffsetFrame(name, body, tuple(float(v) for v in translation), path)
+        fr = OffsetFrame(name, body, tuple(float(v) for v in translation), path,
+                         tuple(float(v) for v in orientation))
         self.offset_frames[path] = fr
         return fr
 
@@ -448,13 +455,44 @@ class Model:
                 return fr.body, tuple(fr.translation)
         return None
 
+    def find_frame_orientation(self, path: str) -> Optional[np.ndarray]:
+        """R_BO, the orientation in its body of the Frame at ``path`` (what
+        find_frame resolves): body_fixed_xyz of an offset frame's angles, the
+        identity for ground and a body; None when there is no such frame."""
+        if self.find_frame(path) is None:
+            return None
+        if path not in ("/ground", "ground") and not any(path in (b, "/bodyset/" + b) for b in self.bodies):
+            for fr in self.offset_frames.values():
+                if path in (fr.path, fr.name):
+                    return body_fixed_xyz(fr.orientation)
+        return np.eye(3)
+
+    def frame_pose_in_ground(self, path: str, coordinates: Dict[str, float]):
+        """(position of the origin, rotation) in ground of the Frame at
+        ``path`` at the given coordinate values (as marker_locations_in_ground
+        takes them): Frame::getPositionInGround / getRotationInGround.  For
+        frame-tracking references computed from states, and for synthesizing
+        data (configs.py); not on the hot path."""
+        fr = self.find_frame(path)
+        if fr is None:
+            raise ValueError(f"no frame '{path}' in the model")
+        X = self._body_transforms_in_ground(coordinates)[fr[0]]
+        return (X @ np.append(np.asarray(fr[1], float), 1.0))[:3], X[:3, :3] @ self.find_frame_orientation(path)
+
     def marker_locations_in_ground(self, coordinates: Dict[str, float]) -> Dict[str, np.ndarray]:
         """Every marker's location in ground (by marker path) at the given
         coordinate values (by coordinate name; a missing one is at its
-        default): the position part of the forward kinematics -- parent pose
-        x joint frames x axis functions -- in NumPy, as 4x4 transforms.  For
-        synthesizing marker data from coordinate trajectories (configs.py);
-        not on the hot path."""
+        default).  For synthesizing marker data from coordinate trajectories
+        (configs.py); not on the hot path."""
+        X_G = self._body_transforms_in_ground(coordinates)
+        return {path: (X_G[mk.body] @ np.append(np.asarray(mk.location, float), 1.0))[:3]
+                for path, mk in self.markers.items()}
+
+    def _body_transforms_in_ground(self, coordinates: Dict[str, float]) -> Dict[str, np.ndarray]:
+        """Every body's transform in ground (and ground's) at the given
+        coordinate values: the position part of the forward kinematics --
+        parent pose x joint frames x axis functions -- in NumPy, as 4x4
+        transforms."""
         from .splines import SimmSpline
 
         def value(f: Function) -> float:
@@ -487,8 +525,7 @@ class Model:
             X_PF = transform(body_fixed_xyz(j.orient_in_parent), j.loc_in_parent)
             X_BM = transform(body_fixed_xyz(j.orient_in_child), j.loc_in_child)
             X_G[j.child] = X_G[j.parent] @ X_PF @ X_FM @ np.linalg.inv(X_BM)
-        return {path: (X_G[mk.body] @ np.append(np.asarray(mk.location, float), 1.0))[:3]
-                for path, mk in self.markers.items()}
+        return X_G
 
     # ordering ---------------------------------------------------------------
     def tree_order(self) -> List[Joint]:
@@ -850,7 +887,8 @@ def model_to_dict(m: Model) -> dict:
         "springs": [{"name": f.name, "coordinate": f.coordinate, "stiffness": f.stiffness,
                      "rest_length": f.rest_length, "viscosity": f.viscosity, "path": f.path}
                     for f in m.springs],
-        **({"offset_frames": [{"name": f.name, "body": f.body, "translation": list(f.translation)}
+        **({"offset_frames": [{"name": f.name, "body": f.body, "translation": list(f.translation),
+                               **({"orientation": list(f.orientation)} if f.oriented() else {})}
                               for f in m.offset_frames.values()]} if m.offset_frames else {}),
     }
 
@@ -891,5 +929,5 @@ def model_from_dict(d: dict) -> Model:
         m.add_spring(SpringGeneralizedForce(f["name"], f["coordinate"], f["stiffness"], f["rest_length"],
                                             f["viscosity"], f.get("path", "")))
     for f in d.get("offset_frames", []):
-        m.add_offset_frame(f["name"], f["body"], tuple(f["translation"]))
+        m.add_offset_frame(f["name"], f["body"], tuple(f["translation"]), tuple(f.get("orientation", (0.0, 0.0, 0.0))))
     return m

@@ -164,6 +164,176 @@ class MocoMarkerTrackingGoal:
     allow_unused_references: bool = False
 
 
+def rotation_to_quaternion(R) -> np.ndarray:
+    """(e0, e1, e2, e3) of the rotation matrix R by the standard four-case
+    method: from the trace when it is the largest of (trace, R00, R11, R22),
+    else from the largest diagonal entry; canonicalised to e0 >= 0 and
+    normalised.  This is Simbody's Rotation::convertRotationToQuaternion as
+    recalled -- Simbody is not at hand, so the convention (case order, sign) is
+    not pinned against it.  q and -q are the same rotation; e0 >= 0 picks one,
+    but near e0 = 0 (a half turn) consecutive rows of a table can still land on
+    opposite signs, and the splined, re-normalised quaternion then passes
+    through garbage between them.  The reference does not repair such flips
+    and neither does this."""
+    R = np.asarray(R, float)
+    tr = R[0, 0] + R[1, 1] + R[2, 2]
+    if tr >= R[0, 0] and tr >= R[1, 1] and tr >= R[2, 2]:
+        q = np.array([1.0 + tr, R[2, 1] - R[1, 2], R[0, 2] - R[2, 0], R[1, 0] - R[0, 1]])
+    elif R[0, 0] >= R[1, 1] and R[0, 0] >= R[2, 2]:
+        q = np.array([R[2, 1] - R[1, 2], 1.0 - (tr - 2.0 * R[0, 0]), R[0, 1] + R[1, 0], R[0, 2] + R[2, 0]])
+    elif R[1, 1] >= R[2, 2]:
+        q = np.array([R[0, 2] - R[2, 0], R[0, 1] + R[1, 0], 1.0 - (tr - 2.0 * R[1, 1]), R[1, 2] + R[2, 1]])
+    else:
+        q = np.array([R[1, 0] - R[0, 1], R[0, 2] + R[2, 0], R[1, 2] + R[2, 1], 1.0 - (tr - 2.0 * R[2, 2])])
+    q = q / math.sqrt(float(q @ q))
+    return -q if q[0] < 0.0 else q
+
+
+@dataclass
+class FrameReference:
+    """A TimeSeriesTableVec3 of frame positions (``values[row][frame][xyz]``)
+    or a TimeSeriesTable_<Rotation> of frame rotations in ground
+    (``values[row][frame][3][3]``), labelled by frame path."""
+    times: Sequence[float] = ()
+    labels: List[str] = field(default_factory=list)
+    values: Optional[np.ndarray] = None
+
+
+@dataclass
+class _FrameTrackingGoal:
+    """What MocoTranslationTrackingGoal and MocoOrientationTrackingGoal share
+    (initializeOnModelImpl of either): the reference given as a table of
+    frame data or as states, the frame_paths selection, the weights.
+
+    The reference is either ``reference`` (a FrameReference) or
+    ``states_reference`` (a DataTable whose labels are state paths; the frame
+    data is computed at each row by forward kinematics), never both.  With a
+    table, an empty ``frame_paths`` tracks every column and a non-empty one
+    selects the named columns -- the documented behaviour; the reference's
+    code tests the property the wrong way round.  With states,
+    ``frame_paths`` is required.  The flattened table (``reference_table``) is
+    a table of the model (Model.add_table) under ``reference_name()``, as a
+    marker goal's is."""
+    name: str = ""
+    weight: float = 1.0
+    reference: Optional[FrameReference] = None
+    states_reference: Optional[DataTable] = None
+    frame_paths: List[str] = field(default_factory=list)
+    frame_weights: Dict[str, float] = field(default_factory=dict)
+    table_name: str = ""
+    degree: int = 5
+
+    WHAT = ""        # "translation" / "rotation", as in the reference's messages
+    SUFFIXES = ()
+
+    def set_weight_for_frame(self, frame_path: str, weight: float):
+        self.frame_weights[frame_path] = float(weight)
+
+    def weight_for_frame(self, frame_path: str) -> float:
+        return float(self.frame_weights.get(frame_path, 1.0))
+
+    def reference_name(self) -> str:
+        return self.table_name or f"{self.name}_reference"
+
+    def tracked_frame_paths(self) -> List[str]:
+        if self.reference is not None and self.states_reference is not None:
+            raise ValueError(f"{type(self).__name__}: a {self.WHAT} reference and a states reference "
+                             "cannot both be given")
+        if self.reference is not None:
+            labels = list(self.reference.labels)
+            if not self.frame_paths:
+                paths = labels
+            else:
+                for path in self.frame_paths:
+                    if path not in labels:
+                        raise ValueError(f"Expected frame_paths to match one of the column labels in the "
+                                         f"{self.WHAT} reference, but frame path '{path}' not found in the "
+                                         "reference labels.")
+                paths = list(self.frame_paths)
+        elif self.states_reference is not None:
+            if not self.frame_paths:
+                raise ValueError("Expected paths in the frame_paths property, but none were found.")
+            paths = list(self.frame_paths)
+        else:
+            raise ValueError(f"{type(self).__name__}: no reference")
+        check_redundant_labels(paths)
+        return paths
+
+    def _frame_values(self, model: Model, paths: List[str]):
+        """times and values[row][frame] (a position or a rotation)."""
+        if self.reference is not None:
+            vals = np.asarray(self.reference.values, float)
+            if vals.shape[:2] != (len(self.reference.times), len(self.reference.labels)):
+                raise ValueError(f"{type(self).__name__}: reference values of shape {vals.shape} for "
+                                 f"{len(self.reference.times)} rows and {len(self.reference.labels)} labels")
+            idx = [self.reference.labels.index(p) for p in paths]
+            return np.asarray(self.reference.times, float), vals[:, idx]
+        ref = self.states_reference
+        states = set()
+        for c in model.coordinates():
+            states.update((c.path + "/value", c.path + "/speed"))
+        for mu in model.muscles:
+            states.update((mu.path + "/activation", mu.path + "/normalized_tendon_force"))
+        for label in ref.columns:          # checkLabelsMatchModelStates
+            if label not in states:
+                raise ValueError(f"Expected the provided labels to match the model state names, but label "
+                                 f"{label} does not correspond to any model state.")
+        bypath = {c.path + "/value": c.name for c in model.coordinates()}
+        cols = {bypath[k]: np.asarray(v, float) for k, v in ref.columns.items() if k in bypath}
+        pick = 0 if self.WHAT == "translation" else 1
+        vals = [[model.frame_pose_in_ground(p, {n: v[r] for n, v in cols.items()})[pick] for p in paths]
+                for r in range(len(ref.times))]
+        return np.asarray(ref.times, float), np.asarray(vals, float)
+
+    def reference_table(self, model: Model) -> DataTable:
+        """The flattened reference: <frame path>/position_x|y|z or
+        <frame path>/quaternion_e0..3 per tracked frame, splined as
+        GCVSplineSet(table) does (degree 5)."""
+        paths = self.tracked_frame_paths()
+        for p in paths:
+            if model.find_frame(p) is None:
+                raise ValueError(f"{type(self).__name__}: no frame '{p}' in the model")
+        times, vals = self._frame_values(model, paths)
+        cols = {}
+        for i, p in enumerate(paths):
+            flat = self._flatten(vals[:, i])
+            for c, sfx in enumerate(self.SUFFIXES):
+                cols[f"{p}/{sfx}"] = np.ascontiguousarray(flat[:, c])
+        return DataTable(self.reference_name(), times, cols, degree=self.degree)
+
+
+@dataclass
+class MocoTranslationTrackingGoal(_FrameTrackingGoal):
+    """MocoTranslationTrackingGoal (Moco/Moco/MocoGoal/
+    MocoTranslationTrackingGoal.{h,cpp}): the integral over the phase of
+    sum_f w_f |origin of model frame f in ground - reference_f(t)|^2, times the
+    weight (include/mocohip.h MH_GOAL_TRANSLATION_TRACKING)."""
+    name: str = "translation_tracking"
+    WHAT = "translation"
+    SUFFIXES = ("position_x", "position_y", "position_z")
+
+    @staticmethod
+    def _flatten(v):
+        return np.asarray(v, float).reshape(len(v), 3)
+
+
+@dataclass
+class MocoOrientationTrackingGoal(_FrameTrackingGoal):
+    """MocoOrientationTrackingGoal (Moco/Moco/MocoGoal/
+    MocoOrientationTrackingGoal.{h,cpp}): the integral over the phase of
+    sum_f w_f theta_f^2, theta_f the angle of the rotation between model frame
+    f and the reference (rotations converted to quaternions,
+    rotation_to_quaternion, splined and re-normalised), times the weight
+    (include/mocohip.h MH_GOAL_ORIENTATION_TRACKING)."""
+    name: str = "orientation_tracking"
+    WHAT = "rotation"
+    SUFFIXES = ("quaternion_e0", "quaternion_e1", "quaternion_e2", "quaternion_e3")
+
+    @staticmethod
+    def _flatten(v):
+        return np.stack([rotation_to_quaternion(R) for R in np.asarray(v, float).reshape(len(v), 3, 3)])
+
+
 # ------------------------------------------------- functions of time ----
 @dataclass
 class Constant:
@@ -503,6 +673,11 @@ class ProblemRep:
                                               "(the coordinates are not NLP states)")
                 gs.kind = abi.MH_GOAL_MARKER_TRACKING
                 self._marker_tracking_terms(model, g, gs, gidx, gcol, gw)
+            elif isinstance(g, (MocoTranslationTrackingGoal, MocoOrientationTrackingGoal)):
+                if kin is not None:
+                    raise NotImplementedError(f"{type(g).__name__} with prescribed kinematics "
+                                              "(the coordinates are not NLP states)")
+                self._frame_tracking_terms(model, g, gs, gidx, gcol, gw)
             elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
                 gs.kind = abi.MH_GOAL_AUX_DERIVATIVES
                 naux = sum(1 for m in model.muscles if not m.ignore_tendon_compliance
@@ -785,6 +960,42 @@ class ProblemRep:
                     raise ValueError(f"reference table {ref.name} has no column '{col}'")
                 gidx.append(body); gcol.append(cols.index(col)); gw.append(float(mk.location[c]))
             gidx.append(body); gcol.append(-1); gw.append(weights[i])
+
+    def _frame_tracking_terms(self, model: Model, g: "_FrameTrackingGoal", gs, gidx, gcol, gw):
+        """MocoTranslationTrackingGoal / MocoOrientationTrackingGoal::
+        initializeOnModelImpl: four terms per tracked frame (kind 9, as a
+        marker's) or ten (kind 10: R_BO, the quaternion columns, the weight);
+        include/mocohip.h."""
+        orient = isinstance(g, MocoOrientationTrackingGoal)
+        gs.kind = abi.MH_GOAL_ORIENTATION_TRACKING if orient else abi.MH_GOAL_TRANSLATION_TRACKING
+        paths = g.tracked_frame_paths()
+        name = g.reference_name()
+        if name not in self.compiled.table_index:
+            raise ValueError(f"reference table {name} not in model")
+        gs.table = self.compiled.table_index[name]
+        cols = self.compiled.table_columns[name]
+        for path in paths:
+            fr = model.find_frame(path)
+            if fr is None:
+                raise ValueError(f"{type(g).__name__}: no frame '{path}' in the model")
+            w = g.weight_for_frame(path)
+            if w < 0:
+                raise ValueError(f"{type(g).__name__}: negative weight {w} of frame '{path}'")
+            body = -1 if fr[0] == "ground" else self.compiled.body_index[fr[0]]
+            ci = []
+            for sfx in g.SUFFIXES:
+                col = f"{path}/{sfx}"
+                if col not in cols:
+                    raise ValueError(f"reference table {name} has no column '{col}'")
+                ci.append(cols.index(col))
+            if orient:
+                R = model.find_frame_orientation(path)
+                for k in range(9):
+                    gidx.append(body); gcol.append(ci[k] if k < 4 else -1); gw.append(float(R[k // 3, k % 3]))
+            else:
+                for c in range(3):
+                    gidx.append(body); gcol.append(ci[c]); gw.append(float(fr[1][c]))
+            gidx.append(body); gcol.append(-1); gw.append(w)
 
     @staticmethod
     def _frame_distance_equations(model: Model, pc: "MocoFrameDistanceConstraint", eqs, frame_terms):
