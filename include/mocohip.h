@@ -914,6 +914,23 @@ int mh_get_work(const mh_ctx* ctx, double* work4);
 int mh_debug_jacobian_lanes(mh_ctx* ctx, const double* x, double* times,
         double* Y);
 
+/* Debug entry, host only (no device, no context): how the fused interval
+ * kernel's overlapped order classifies the entries of the block-dense
+ * interval pattern (one mesh interval's entries, then the tail's).  An early
+ * entry (1) reads only LDS constants or outputs that copy a group result and
+ * is assembled while the solve chain runs; every other entry is late (0).
+ * info8 = {entries, entries of an interval, points per interval, callback
+ * outputs NO, lanes per point S, directions ND, finite-difference scheme,
+ * base lane}.  With cap >= max(entries, NO) the call also fills words /
+ * bases / early [entries] (the compiled word, the LDS offset of its row's
+ * base lane, the class) and out_early [NO] (the output is a group-result
+ * copy); with a smaller cap only info8 (a size query).  A word's bits 0-19
+ * are its LDS offset relative to the lane outputs ([point][output][lane];
+ * offsets from points x NO x S on are constants), bit 27 marks a t0 / tf or
+ * parameter column and bit 28 a path-constraint entry (both late). */
+int mh_debug_interval_overlap(const mh_problem* problem, const mh_options* options, int32_t* info8,
+        uint32_t* words, uint32_t* bases, uint8_t* early, uint8_t* out_early, int64_t cap);
+
 /* Benchmark entry: average device duration of each stage of eval_jac_g
  * (kind 1) or eval_g (kind 0) at the device iterate x_dev, over reps
  * (at most 500) evaluations of both stages in their call order with a HIP

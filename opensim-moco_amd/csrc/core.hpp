@@ -910,6 +910,14 @@ struct Interval {
     int dbase;
     uint32_t smagic, sstride, sbase;
     int qdiv;        // k_transcribe's quotients by div_rn (1, MOCOHIP_QDIV=1) or the division (0)
+    // k_interval's overlapped order (interval_body): the entries assembled
+    // while the solve chain runs (early) and after it (late; without the
+    // CT_GEN / CT_PATH entries, which have loops of their own), each list as
+    // entry index [n], word [n], base word [n], entries ascending with the
+    // tail's last.  ovl = [early lists (3 ov_ne[1])][late lists (3 ov_nl[1])];
+    // ov_n*[0]: an interval's entries, [1]: with the tail's
+    const uint32_t* ovl;
+    int ov_ne[2], ov_nl[2];
     __device__ __forceinline__ uint32_t base_of(uint32_t w, uint32_t nyall) const {
         const uint32_t off = w & CT_OFF;
         const bool lane = !(w & (CT_GEN | CT_PATH)) && off < nyall;
@@ -1343,7 +1351,10 @@ constexpr int CT_NCONST = 12;
 // SLDS: the role -> slot table staged in LDS with the group results (the
 // Jacobian lanes' combine then reads its slots from LDS instead of global
 // memory after the barrier; MOCOHIP_IV_SLOTS_LDS=1).
-template <class D, bool GM, bool BASE = false, bool SLDS = false>
+// OV: the overlapped order (below), launched for the Jacobian lanes of the
+// compiled template with fused quotients when the workgroup has waves
+// besides the combine lanes' (mh_create: c->iv_overlap).
+template <class D, bool GM, bool BASE = false, bool SLDS = false, bool OV = false>
 __device__ __forceinline__ void interval_body(const DevModel& M, const Src& S, const Lanes& Ln, const Tasks& TK,
         const Layout& L, const Interval& I, const TplEntry* __restrict__ tpl, const uint32_t* __restrict__ ctpl,
         const int* __restrict__ ctgen, int nctgen,
@@ -1405,12 +1416,23 @@ __device__ __forceinline__ void interval_body(const DevModel& M, const Src& S, c
     // eval_g's lanes (stride 1: every lane is the base role 0, written as a
     // constant so that the role -> slot reads have uniform addresses and
     // compile to scalar loads off the combine's critical path)
-    auto combine_lane = [&](int p, int r) {
+    // PART: 0 the whole combine; the overlapped order's two parts: 1 the
+    // group-result copies (D::combine_copies), 2 the rest (D::combine_solved)
+    using PartAll = std::integral_constant<int, 0>;
+    using PartCopies = std::integral_constant<int, 1>;
+    using PartSolved = std::integral_constant<int, 2>;
+    auto combine_lane = [&](int p, int r, auto partc) {
+        constexpr int PART = decltype(partc)::value;
         LaneInL<D> in{lds(sXs + p * L.NS), lds(sXc + p * L.NC), lds(sXd + p * L.NDV), -1, 0.0,
                       lds(sXm + p * L.NM), L.vc(k_first + p) ? lds(sXl) : nullptr};
         const double t = lane_time(Ln, S.grid[k_first + p], t0, tf, r, in.pi, in.step);
-        if (r == Ln.base) sTimes[p] = t;
+        if (PART != 2 && r == Ln.base) sTimes[p] = t;
         const LdsOut out{lds(sY + p * ny + r), Ln.stride};
+        auto run = [&](const auto& TL) {
+            if constexpr (PART == 1) D::combine_copies(M, t, in, TL, out);
+            else if constexpr (PART == 2) D::combine_solved(M, t, in, TL, out);
+            else D::combine(M, t, in, TL, out);
+        };
         if constexpr (BASE) {   // (BASE && GM combined before the staging, above)
             const TaskLoadBase<D, const lds_double*> TL{lds(sT + p * nt), lds(sH + p * nh)};
             D::combine(M, t, in, TL, out);
@@ -1419,23 +1441,144 @@ __device__ __forceinline__ void interval_body(const DevModel& M, const Src& S, c
             D::combine(M, t, in, TL, out);
         } else if constexpr (SLDS) {
             const TaskLoadLds<D, const lds_int*> TL{lds(sT + p * nt), lds(sH + p * nh), (const lds_int*)sSl, r};
-            D::combine(M, t, in, TL, out);
+            run(TL);
         } else {
             const TaskLoadLds<D> TL{lds(sT + p * nt), lds(sH + p * nh), TK.jd, r};
-            D::combine(M, t, in, TL, out);
+            run(TL);
         }
     };
+    if constexpr (OV && !BASE && !GM) {
+        {
+            // The overlapped order.  Most Jacobian entries read only outputs
+            // that copy a group result (D::OUT_EARLY; gait: the activation
+            // rows) or LDS constants: the host lists them (early) apart from
+            // the entries that read a solved output (late).  (a) the combine
+            // lanes copy; (b) their waves run the solve chain while every
+            // other wave assembles the early list; (c) all waves assemble the
+            // rest.  The same arithmetic per output and per entry as the
+            // order below, bit for bit.  Every branch around a barrier is
+            // uniform over the workgroup; the (b) split is by whole waves.
+#pragma clang fp contract(off)
+            const int B = blockDim.x, tid = threadIdx.x;
+            const int nl = npts * Ln.stride;       // combine lanes (nl <= ncw * 64 < B: mh_create)
+            const int ncw = (nl + 63) >> 6;        // their waves
+            const int cp = tid / Ln.stride, cr = tid - cp * Ln.stride;
+            if (tid < nl) combine_lane(cp, cr, PartCopies{});
+            if (tid == B - 1) {
+                // the coefficient / base tables the words select from, by a
+                // thread with no lane to combine: the base lanes' times of the
+                // first and last point as combine_lane forms them
+                int pi;
+                double st;
+                const double ta = lane_time(Ln, S.grid[k_first], t0, tf, Ln.base, pi, st);
+                const double tb = lane_time(Ln, S.grid[k_last], t0, tf, Ln.base, pi, st);
+                const IvC C0 = iv_const(tb - ta, S.grid[k_last] - S.grid[k_first]);
+                sK[2] = 0.0; sK[3] = -C0.h8; sK[4] = C0.h8; sK[5] = -C0.h6; sK[6] = -C0.h6 * 4.0; sK[7] = -C0.hh;
+                sK[8] = 0.0; sK[9] = -0.5; sK[10] = 1.0; sK[11] = -1.0;
+            }
+            __syncthreads();
+            double* vi = values + (long)il * I.nnz_int;
+            const lds_double* q0 = lds(sY);
+            const lds_double* kc = lds(sK + 2);
+            const lds_double* kb = lds(sK + 8);
+            const int nyall = npts * ny;
+            const double h1 = Ln.h, h2 = 2.0 * Ln.h;
+            // entries j0, j0 + J, .. of a list (index, word, base word), the
+            // fused-quotient arithmetic of the order below (bulk: qat, value)
+            auto run_list = [&](auto fdc, const uint32_t* __restrict__ le, int cap, int n, int j0, int J) {
+                constexpr int FD = decltype(fdc)::value;
+                const uint32_t* __restrict__ lw = le + cap;
+                const uint32_t* __restrict__ lb = lw + cap;
+                auto value = [&](uint32_t wu, double q) {
+                    const double coef = kc[(wu >> 20) & 7], base = kb[(wu >> 23) & 7];
+                    return (wu & CT_RAW) ? q : base + coef * q;
+                };
+                auto qat = [&](uint32_t off, uint32_t boff) -> double {
+                    const double y = q0[off];
+                    const bool lane = (int)off < nyall;
+                    const double ym = FD == MH_FD_CENTRAL ? q0[lane ? off + Ln.ND : off] : q0[boff];
+                    const double qd = FD == MH_FD_CENTRAL ? (y - ym) / h2
+                                    : FD == MH_FD_FORWARD ? (y - ym) / h1 : (ym - y) / h1;
+                    return lane ? qd : y;
+                };
+                int j = j0;
+                for (; j + (IV_UNROLL - 1) * J < n; j += IV_UNROLL * J) {
+                    uint32_t e[IV_UNROLL], w[IV_UNROLL], wb[IV_UNROLL];
+                    double q[IV_UNROLL];
+#pragma unroll
+                    for (int u = 0; u < IV_UNROLL; ++u) {
+                        e[u] = le[j + u * J];
+                        w[u] = lw[j + u * J];
+                        wb[u] = lb[j + u * J];
+                    }
+#pragma unroll
+                    for (int u = 0; u < IV_UNROLL; ++u) q[u] = qat(w[u] & CT_OFF, wb[u]);
+#pragma unroll
+                    for (int u = 0; u < IV_UNROLL; ++u) vi[e[u]] = value(w[u], q[u]);
+                }
+                for (; j < n; j += J) {
+                    const uint32_t wu = lw[j];
+                    vi[le[j]] = value(wu, qat(wu & CT_OFF, lb[j]));
+                }
+            };
+            auto assemble = [&](const uint32_t* le, int cap, int n, int j0, int J) {
+                if (Ln.fd == MH_FD_FORWARD) run_list(std::integral_constant<int, MH_FD_FORWARD>{}, le, cap, n, j0, J);
+                else if (Ln.fd == MH_FD_BACKWARD)
+                    run_list(std::integral_constant<int, MH_FD_BACKWARD>{}, le, cap, n, j0, J);
+                else run_list(std::integral_constant<int, MH_FD_CENTRAL>{}, le, cap, n, j0, J);
+            };
+            const int last = i == I.N - 1;
+            if ((tid >> 6) < ncw) {
+                if (tid < nl) combine_lane(cp, cr, PartSolved{});
+            } else if (I.dbg_stop != 2) {
+                assemble(I.ovl, I.ov_ne[1], I.ov_ne[last], tid - ncw * 64, B - ncw * 64);
+            }
+            __syncthreads();
+            // (diagnostic cuts: 2 the staging and the combine alone, 8 with
+            // the early assembly beside the combine)
+            if (I.dbg_stop == 2 || I.dbg_stop == 8) return;
+            const YS YV{lds(sY), lds(sTimes), D::NO, Ln.stride, k_first, 0, lds(sXs), lds(sXc), L.NS, L.NC,
+                        lds(sXd), L.NDV};
+            // (the g rows last: the late words' loads do not wait behind the
+            // rows' stores; cut 4 keeps its meaning, the g rows without the
+            // assembly after the combine)
+            auto g_rows = [&]() {
+                if (!g) return;
+                double* gi = g + (long)il * I.rpi;
+                for (int r = tid; r < I.rows(i); r += B) gi[r] = defect_row(L, I, Ln, S.x, YV, i, r);
+            };
+            if (I.dbg_stop == 4) { g_rows(); return; }
+            assemble(I.ovl + 3 * (long)I.ov_ne[1], I.ov_nl[1], I.ov_nl[last], tid, B);
+            const IvC C = iv_const(YV.t(k_last) - YV.t(k_first), S.grid[k_last] - S.grid[k_first]);
+            for (int j = tid; j < nctgen; j += B) {
+                const int eg = ctgen[j];
+                vi[eg] = jac_entry<false>(L, Ln, I.P, S.x, YV, tpl[eg], k_first, C);
+            }
+            if (I.npe > 0) {
+                const int npe = I.npe;
+                const int nw = last ? 2 * npe : npe;
+                for (int w = tid; w < nw; w += B) {
+                    const int ep = w < npe ? w : I.nnz_int + (w - npe);
+                    vi[ep] = jac_entry<true>(L, Ln, I.P, S.x, YV, tpl[ep], k_first, C);
+                }
+            }
+            g_rows();
+            if (i == 0 && (I.gh || I.vh))
+                endpoint_head(L, Ln, I.E, S.x, g ? I.gh : nullptr, I.vh, tid, B);
+            return;
+        }
+    }
     // (one thread per lane role: the combine split over the waves --
     // D::combine_sum into LDS, then D::combine_finish -- measured slower:
     // k_interval 17.6 -> 19.7 us, eval_g's 9.9 -> 10.6 us, profiles/r05_b;
     // the combine is not bound by its sums' load-and-add chains)
     if constexpr (BASE && GM) {
     } else if (BASE || Ln.stride == 1) {
-        if ((int)threadIdx.x < npts) combine_lane((int)threadIdx.x, 0);
+        if ((int)threadIdx.x < npts) combine_lane((int)threadIdx.x, 0, PartAll{});
     } else {
         for (int w = threadIdx.x; w < npts * Ln.stride; w += blockDim.x) {
             const int p = w / Ln.stride, r = w - p * Ln.stride;
-            combine_lane(p, r);
+            combine_lane(p, r, PartAll{});
         }
     }
     // the compiled words of this thread's first IV_PF assembly entries,
@@ -1637,7 +1780,7 @@ __device__ __forceinline__ void interval_body(const DevModel& M, const Src& S, c
 // = 256) take the 256-thread instantiation: its combine lanes may keep up to
 // 512 VGPRs, where the 1024-thread bound (128) made a large model's combine
 // spill (Rajagopal 80: 2.9 KB of scratch per lane, ~150 us per eval_g).
-template <class D, int MAXT = 1024, bool BASE = false, bool GM = false, bool SLDS = false>
+template <class D, int MAXT = 1024, bool BASE = false, bool GM = false, bool SLDS = false, bool OV = false>
 __global__ void __launch_bounds__(MAXT) k_interval(DevModel M, Src S, Lanes Ln, Tasks TK, Layout L,
         Interval I, const TplEntry* __restrict__ tpl, const uint32_t* __restrict__ ctpl,
         const int* __restrict__ ctgen, int nctgen,
@@ -1646,7 +1789,7 @@ __global__ void __launch_bounds__(MAXT) k_interval(DevModel M, Src S, Lanes Ln, 
     // il0: the first interval of this launch within the shard (a chunked
     // assembly, whose chunks are copied to the host while the next runs)
     const int b = (int)blockIdx.x;
-    interval_body<D, GM, BASE, SLDS>(M, S, Ln, TK, L, I, tpl, ctpl, ctgen, nctgen, T, H, g, values,
+    interval_body<D, GM, BASE, SLDS, OV>(M, S, Ln, TK, L, I, tpl, ctpl, ctgen, nctgen, T, H, g, values,
                                      il0 + (I.xcd ? xcd_interval(b, (int)gridDim.x) : b));
 }
 
@@ -2242,6 +2385,8 @@ struct TaskInfo {
     const unsigned char* time;         // [ng] group reads the time
     const double* gflops;              // [ng] FP64 ops per group evaluation
     double combine_flops;
+    int no;                            // callback outputs
+    const unsigned char* out_early;    // [no] output is a pure group-result copy (D::OUT_EARLY)
 };
 
 // Task tables for one lane configuration (host copy + device view).
@@ -2395,6 +2540,11 @@ struct mh_ctx {
     uint32_t* d_ctpl = nullptr;    // compiled template of the Jacobian lanes (k_interval)
     std::vector<uint32_t> ctpl;
     int* d_ctgen = nullptr;        // the entries it leaves to jac_entry (t0 / tf of defect rows)
+    // k_interval's overlapped order (Interval::ovl; MOCOHIP_IV_OVERLAP=0: today's order)
+    int iv_overlap = 0;
+    std::vector<uint32_t> ovl;
+    uint32_t* d_ovl = nullptr;
+    int ov_ne[2] = {0, 0}, ov_nl[2] = {0, 0};
     std::vector<int> ctgen;
     // k_role: per role (grid point of the interval) the entries it writes
     // and their words compiled against the role's own-point LDS layout
@@ -2490,7 +2640,7 @@ inline Interval make_interval(const mh_ctx* c, double*& g, double*& v) {
     Interval I{c->scheme, c->interp, c->ib, c->rpi, c->nnz_int, c->NMB + c->NAR, c->NMB, c->NQ + c->NZ,
                c->N, c->nnz_tail, c->ntail, c->npe, c->NK, c->OKC, c->P, c->E, nullptr, nullptr, c->iv_dbg_stop, c->iv_pf, c->iv_qfuse,
                c->iv_xcd, c->iv_dbase, c->iv_smagic, c->iv_sstride, c->iv_sbase,
-               c->iv_qdiv};
+               c->iv_qdiv, c->d_ovl, {c->ov_ne[0], c->ov_ne[1]}, {c->ov_nl[0], c->ov_nl[1]}};
     if (c->ib == 0 && c->nep > 0) {
         I.gh = g;
         I.vh = v;
@@ -2805,6 +2955,9 @@ static void be_interval(mh_ctx* c, const double* x, int mode, double* g, double*
 #if MOCOHIP_AB_VARIANTS
     if (v && threads > 256 && c->iv_slots_lds && ln.stride > 1) kern = k_interval<D, 1024, false, false, true>;
 #endif
+    // the Jacobian lanes' overlapped order (MOCOHIP_IV_OVERLAP=0: the plain one)
+    if (v && mode == 1 && c->iv_overlap && c->use_ctpl && threads > 256 && kern == k_interval<D, 1024>)
+        kern = k_interval<D, 1024, false, false, false, true>;
     if (!v && ln.stride == 1 && threads <= 256 && c->ivg_base) {
         const bool gm = c->ivg_gm < 0 ? ts.dev.tdoubles <= kIvgGmMaxDoubles : c->ivg_gm != 0;
         kern = gm ? k_interval<D, 256, true, true> : k_interval<D, 256, true>;
@@ -2861,7 +3014,7 @@ static constexpr Backend make_backend_lane(const char* name, double flops) {
 template <class D>
 struct TaskInfoOf {
     static constexpr TaskInfo value{D::NG, D::NST, D::NF, D::RW, D::NHEAVY, D::GROUP_NF, &D::GROUP_READS[0][0],
-                                    D::GROUP_TIME, D::GROUP_FLOPS, D::COMBINE_FLOPS};
+                                    D::GROUP_TIME, D::GROUP_FLOPS, D::COMBINE_FLOPS, D::NO, D::OUT_EARLY};
 };
 template <class D>
 static constexpr Backend make_backend_tasks(const char* name, double flops) {

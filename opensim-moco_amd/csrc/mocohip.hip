@@ -1468,6 +1468,78 @@ static bool compile_template(mh_ctx* c) {
     return true;
 }
 
+// k_interval's overlapped order (core.hpp interval_body): the class of every
+// entry of the interval pattern, the tail included, from its compiled word
+// (words[0..nw)) and base word (words[nw..2 nw)).  Early (1): the entry can be
+// assembled as soon as the group-result copies are in LDS -- not a CT_GEN /
+// CT_PATH entry, and every LDS offset it reads (the word's, its row's base
+// lane, the mirror lane of a central difference) is a constant past the lanes
+// or a lane of an output D::combine_copies writes (out_early).  Late (0):
+// everything else.  Plain host code (no device, no context).
+static void classify_overlap(const uint32_t* words, size_t nw, int npts, int NO, int stride, int ND, int fd,
+        const unsigned char* out_early, uint8_t* early) {
+    const uint32_t nyall = (uint32_t)(npts * NO * stride);
+    auto ready = [&](uint32_t off) {
+        if (off >= nyall) return true;
+        return out_early != nullptr && out_early[(off / (uint32_t)stride) % (uint32_t)NO] != 0;
+    };
+    for (size_t e = 0; e < nw; ++e) {
+        const uint32_t w = words[e], off = w & CT_OFF;
+        bool ok = !(w & (CT_GEN | CT_PATH)) && ready(off);
+        if (ok && off < nyall) {
+            ok = ready(words[nw + e]);
+            if (fd == MH_FD_CENTRAL) ok = ok && (int)(off % (uint32_t)stride) < ND && ready(off + (uint32_t)ND);
+        }
+        early[e] = ok ? 1 : 0;
+    }
+}
+
+// The early / late entry lists of c->ctpl (Interval::ovl) after the last
+// change of the words (redirect_exc_words, a detected template).  False when
+// an early entry would read an LDS word the copy phase does not write (the
+// early reads and combine_solved's writes must be disjoint), or the lists do
+// not cover the pattern.
+static bool build_overlap_lists(mh_ctx* c, const TaskInfo& ti) {
+    const size_t nw = (size_t)c->nnz_int + (size_t)c->nnz_tail;
+    const Lanes& ln = c->lanes_jac;
+    const int npts = c->scheme == MH_HERMITE_SIMPSON ? 3 : 2;
+    if (c->ctpl.size() < 2 * nw || ti.no != c->NO) return false;
+    std::vector<uint8_t> early(nw);
+    classify_overlap(c->ctpl.data(), nw, npts, c->NO, ln.stride, ln.ND, ln.fd, ti.out_early, early.data());
+    std::vector<uint32_t> le[2], lw[2], lb[2];   // [0] early, [1] late
+    for (int k = 0; k < 2; ++k) c->ov_ne[k] = c->ov_nl[k] = 0;
+    size_t skipped = 0;
+    for (size_t e = 0; e < nw; ++e) {
+        const uint32_t w = c->ctpl[e];
+        if (w & (CT_GEN | CT_PATH)) { ++skipped; continue; }   // the ctgen / path loops'
+        const int k = early[e] ? 0 : 1;
+        le[k].push_back((uint32_t)e);
+        lw[k].push_back(w);
+        lb[k].push_back(c->ctpl[nw + e]);
+        int* n = k ? c->ov_nl : c->ov_ne;
+        if (e < (size_t)c->nnz_int) ++n[0];
+        ++n[1];
+    }
+    if (le[0].size() + le[1].size() + skipped != nw) return false;
+    // the early reads against the copy phase's writes, offset by offset
+    const uint32_t nyall = (uint32_t)(npts * c->NO * ln.stride);
+    auto written = [&](uint32_t off) {
+        return off >= nyall || ti.out_early[(off / (uint32_t)ln.stride) % (uint32_t)c->NO] != 0;
+    };
+    for (size_t j = 0; j < le[0].size(); ++j) {
+        const uint32_t off = lw[0][j] & CT_OFF;
+        if (off >= nyall + CT_CONST + CT_NCONST || !written(off)) return false;
+        if (off < nyall && !written(ln.fd == MH_FD_CENTRAL ? off + (uint32_t)ln.ND : lb[0][j])) return false;
+    }
+    c->ovl.clear();
+    for (int k = 0; k < 2; ++k) {
+        c->ovl.insert(c->ovl.end(), le[k].begin(), le[k].end());
+        c->ovl.insert(c->ovl.end(), lw[k].begin(), lw[k].end());
+        c->ovl.insert(c->ovl.end(), lb[k].begin(), lb[k].end());
+    }
+    return true;
+}
+
 static const int kZeroInt = 0;
 
 // The objective partial of a shard (mh_eval_f_partial): the quadrature
@@ -2163,6 +2235,9 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     const size_t o_ctgen = A.put(c->ctgen.data(), c->ctgen.size());
     const size_t o_rl_e = A.put(c->rl_e.data(), c->rl_e.size());
     const size_t o_rl_w = A.put(c->rl_w.data(), c->rl_w.size());
+    // k_interval's early / late lists (three words per listed entry)
+    const size_t ovl_cap = 3 * ((size_t)c->nnz_int + (size_t)c->nnz_tail);
+    const size_t o_ovl = A.reserve(sizeof(uint32_t) * std::max<size_t>(ovl_cap, 1));
 
     const int nint = c->ie - c->ib;
     const int ND = c->NI + 2 + c->NPAR;   // t0, tf, the point inputs, the parameters
@@ -2402,6 +2477,7 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     c->d_tpl = (TplEntry*)(b + o_tpl);
     c->d_ctpl = (uint32_t*)(b + o_ctpl);
     c->d_ctgen = (int*)(b + o_ctgen);
+    c->d_ovl = (uint32_t*)(b + o_ovl);
     c->d_rl_e = (int*)(b + o_rl_e);
     c->d_rl_w = (uint32_t*)(b + o_rl_w);
     if (c->has_fdist) {
@@ -2553,6 +2629,26 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
         }
         for (int mode = 0; mode < 2; ++mode)
             c->use_interval[mode] = allow && interval_fits(c.get(), mode);
+        // k_interval's overlapped order (core.hpp interval_body): the early
+        // assembly beside the solve chain; MOCOHIP_IV_OVERLAP=0 keeps the
+        // plain order through the same kernel.  For the compiled template
+        // with fused quotients, a workgroup with waves besides the combine
+        // lanes', and not under the cuts that time the plain assembly's parts
+        // (MOCOHIP_IV_DEBUG_STOP 3, 5, 6)
+        const char* eio = std::getenv("MOCOHIP_IV_OVERLAP");
+        const int npts_ov = c->scheme == MH_HERMITE_SIMPSON ? 3 : 2;
+        const int ncw = (npts_ov * c->lanes_jac.stride + 63) / 64;
+        const int ds = c->iv_dbg_stop;
+        if (!(eio && std::strcmp(eio, "0") == 0) && tib && c->use_interval[1] && c->use_ctpl && c->iv_qfuse &&
+                !c->use_roles && c->lanes_jac.stride > 1 && c->iv_threads > 256 && c->iv_threads / 64 > ncw &&
+                ds != 3 && ds != 5 &&
+                ds != 6) {
+            if (!build_overlap_lists(c.get(), *tib) || c->ovl.size() > ovl_cap)
+                return set_err(MH_ERR_INVALID, "internal: k_interval's early entries read a solved output");
+            if (!c->ovl.empty())
+                HIPCHK(hipMemcpy(c->d_ovl, c->ovl.data(), sizeof(uint32_t) * c->ovl.size(), hipMemcpyHostToDevice));
+            c->iv_overlap = 1;
+        }
     }
     for (auto& e : c->ev) HIPCHK(hipEventCreate(&e));
     if (const char* ek = std::getenv("MOCOHIP_D2H_CHUNKS"))
@@ -3909,6 +4005,42 @@ extern "C" int mh_backend_for(const mh_problem* p, const mh_options* o, char* na
     return MH_OK;
 }
 
+// The early / late classes of k_interval's overlapped order for a problem's
+// block-dense interval pattern, without a device: info = {entries (interval +
+// tail), interval entries, points per interval, outputs, lanes per point,
+// directions, finite-difference scheme, base lane}; with cap >= entries also
+// the compiled words, their base words, the classes (1 early) and, per output,
+// whether the back end's combine_copies writes it.  (mh_create classifies the
+// same words after redirect_exc_words, which moves a word to the base lane
+// of the same output.)
+extern "C" int mh_debug_interval_overlap(const mh_problem* p, const mh_options* o, int32_t* info8, uint32_t* words,
+        uint32_t* bases, uint8_t* early, uint8_t* out_early, int64_t cap) {
+    if (!p || !o || !info8) return set_err(MH_ERR_INVALID, "bad argument");
+    std::unique_ptr<mh_ctx> c(new mh_ctx());
+    std::vector<int> coord_body, act_state, ftn_state, mus_control;
+    double tau_act, tau_deact;
+    int rc = validate_and_layout(c.get(), p, o, coord_body, act_state, ftn_state, mus_control, tau_act,
+            tau_deact);
+    if (rc) return rc;
+    const Backend* be = select_backend(c.get(), p);
+    if (!compile_template(c.get())) return set_err(MH_ERR_UNSUPPORTED, "Jacobian template does not compile");
+    const size_t nw = (size_t)c->nnz_int + (size_t)c->nnz_tail;
+    const int ND = c->NI + 2 + c->NPAR;
+    const int stride = c->fd == MH_FD_CENTRAL ? 2 * ND + 1 : ND + 1;
+    const int npts = c->scheme == MH_HERMITE_SIMPSON ? 3 : 2;
+    const int32_t info[8] = {(int32_t)nw, c->nnz_int, npts, c->NO, stride, ND, c->fd, stride - 1};
+    std::copy(info, info + 8, info8);
+    if (cap < (int64_t)nw || cap < c->NO) return MH_OK;
+    if (!words || !bases || !early || !out_early) return set_err(MH_ERR_INVALID, "null argument");
+    const TaskInfo* ti = be->tasks;
+    for (int q = 0; q < c->NO; ++q) out_early[q] = ti && ti->no == c->NO ? ti->out_early[q] : 0;
+    std::copy(c->ctpl.begin(), c->ctpl.begin() + nw, words);
+    std::copy(c->ctpl.begin() + nw, c->ctpl.begin() + 2 * nw, bases);
+    classify_overlap(c->ctpl.data(), nw, npts, c->NO, stride, ND, c->fd, ti && ti->no == c->NO ? ti->out_early : nullptr,
+            early);
+    return MH_OK;
+}
+
 extern "C" int mh_get_callback_sparsity(const mh_ctx* c, uint8_t* pattern, int64_t len) {
     if (!c || !pattern) return set_err(MH_ERR_INVALID, "null argument");
     const size_t W = 1 + (size_t)c->NI, nd = (size_t)c->NO * W, np = nd + (size_t)c->npc * W;
@@ -3931,6 +4063,7 @@ extern "C" int mh_get_backend_flags(const mh_ctx* c, char* flags, int32_t len) {
     if (c->iv_dbase) f += " dbase";
     if (c->iv_qdiv) f += " qdiv";
     if (c->use_roles && c->use_interval[1]) f += " roles";
+    if (c->iv_overlap && c->use_interval[1]) f += " iv-overlap";
     if (c->quot) f += " quot";
     if (c->asm_grid_stride) f += " asm-gs";
     if (c->d_exc) f += " exc-lanes";

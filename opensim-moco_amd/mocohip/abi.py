@@ -260,6 +260,8 @@ MOCOHIP_SYMBOLS = {
     "mh_get_jacobian_seeds": (i32, [C.c_void_p, P(i32), P(i32)]),
     "mh_debug_jacobian_lanes": (i32, [C.c_void_p, P(f64), P(f64), P(f64)]),
     "mh_debug_time_stages": (i32, [C.c_void_p, C.c_void_p, i32, i32, P(f64)]),
+    "mh_debug_interval_overlap": (i32, [P(mh_problem), P(mh_options), P(i32), P(C.c_uint32), P(C.c_uint32),
+                                        P(C.c_uint8), P(C.c_uint8), C.c_int64]),
     "mh_set_stream": (i32, [C.c_void_p, C.c_void_p]),
     "mh_set_async": (i32, [C.c_void_p, i32]),
     "mh_batch_create": (i32, [C.POINTER(C.c_void_p), i32, C.POINTER(C.c_void_p)]),

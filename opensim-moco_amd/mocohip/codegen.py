@@ -1240,6 +1240,17 @@ def generate(cm, struct_name: str, implicit: bool = False, prescribed: bool = Fa
                            "const double* __restrict__ in, double* __restrict__ out", body))
     parts.append(("combine", "const mh::DevModel& M, const double t, const double* __restrict__ in, "
                              "const TL& T, OUT out", comb))
+    # the same combine in two parts for k_interval's overlapped order: the
+    # group-result copies (OUT_EARLY marks the outputs they write), then
+    # everything else -- sums, factorization, solves, the solved and the
+    # kinematic-constraint outputs
+    cop, early = _emit_combine_copies(Lo, groups)
+    solved, _ = _emit_combine(M, Lo, groups, copy_outputs=False)
+    parts.append(("combine_copies", "const mh::DevModel& M, const double t, "
+                                    "const double* __restrict__ in, const TL& T, OUT out", cop))
+    parts.append(("combine_solved", "const mh::DevModel& M, const double t, "
+                                    "const double* __restrict__ in, const TL& T, OUT out", solved))
+    info["out_early"] = early
     # the same combine in two steps (core.hpp interval_body's split combine):
     # its independent sums one at a time, then the rest from the sums
     nsum, sums_body, consts, sum_flops = _emit_combine_sums(M, Lo, groups)
@@ -1254,12 +1265,14 @@ def generate(cm, struct_name: str, implicit: bool = False, prescribed: bool = Fa
     fns = []
     for name, args, lines in parts:
         tpl = ""
-        if name in ("group", "combine", "combine_sum", "combine_finish"):
+        if name in ("group", "combine", "combine_copies", "combine_solved", "combine_sum", "combine_finish"):
             # inputs through an accessor (loaded where used, not held in VGPRs)
             # combine: outputs through a writer (OUT: a pointer, or a strided
             # Y / LDS writer -- each output is stored as it is produced
             # instead of living in registers until the end)
             tpl = {"group": "template <class IN> ", "combine": "template <class IN, class TL, class OUT> ",
+                   "combine_copies": "template <class IN, class TL, class OUT> ",
+                   "combine_solved": "template <class IN, class TL, class OUT> ",
                    "combine_sum": "template <class IN, class TL> ",
                    "combine_finish": "template <class IN, class TL, class SUMS, class OUT> "}[name]
             args = args.replace("const double* __restrict__ in", "const IN& in")
@@ -1289,6 +1302,9 @@ def generate(cm, struct_name: str, implicit: bool = False, prescribed: bool = Fa
     static constexpr unsigned char GROUP_TIME[NG] = {lst([int(gr.time) for gr in groups])};
     static constexpr double GROUP_FLOPS[NG] = {lst([float(gr.flops) for gr in groups])};
     static constexpr double COMBINE_FLOPS = {float(comb_flops)};
+    // outputs combine_copies() writes (pure copies of a group result); every
+    // other output is combine_solved()'s
+    static constexpr unsigned char OUT_EARLY[NO > 0 ? NO : 1] = {lst([int(o in early) for o in range(max(Lo.NO, 1))])};
     // the combine's independent sums (combine_sum / combine_finish)
     static constexpr int NSUM = {nsum};
     // the model's constant pool (DevModel::pool, filled by fill())
@@ -1497,11 +1513,38 @@ def _emit_groups(M: ModelView, Lo: _Layout) -> List[_Group]:
     return out
 
 
-def _emit_combine(M: ModelView, Lo: _Layout, groups: List[_Group]):
+def _combine_copies(Lo: _Layout, groups: List[_Group]):
+    """The combine's outputs that copy a group result as (output, group,
+    field): the z outputs and the auxiliary residuals."""
+    copies = []
+    for gi, gr in enumerate(groups[1:], start=1):
+        for f, (kind, zi) in enumerate(gr.fields):
+            if kind == "z":
+                copies.append((Lo.NQ + zi, gi, f))
+            elif kind == "r":
+                copies.append((Lo.NQ + Lo.NZ + zi, gi, f))
+    return copies
+
+
+def _emit_combine_copies(Lo: _Layout, groups: List[_Group]):
+    """combine_copies(): the group-result copies of combine() alone (the same
+    T reads, the same out targets).  They need no sum, factorization or
+    solve, so k_interval's overlapped order (core.hpp interval_body) fills
+    them first and assembles the Jacobian entries that read only them while
+    combine_solved() runs.  Returns (lines, the outputs written)."""
+    g = Gen()
+    copies = _combine_copies(Lo, groups)
+    _emit_outputs(g, [], copies)
+    return g.lines, sorted(o for o, _, _ in copies)
+
+
+def _emit_combine(M: ModelView, Lo: _Layout, groups: List[_Group], copy_outputs: bool = True):
     """Per-lane combine: generalized forces summed over the groups in a fixed
     order (so re-using a group's unperturbed result is bit-identical to
     re-evaluating it), coordinate actuators, the two triangular solves with
-    the mass-matrix factor, and the z outputs of the groups."""
+    the mass-matrix factor, and the z outputs of the groups.
+    copy_outputs=False: combine_solved(), everything but the group-result
+    copies (combine_copies() writes those)."""
     NQ = Lo.NQ
     E = _Emitter(M, Lo)
     g = E.g
@@ -1554,7 +1597,7 @@ def _emit_combine(M: ModelView, Lo: _Layout, groups: List[_Group]):
                 copies.append((NQ + Lo.NZ + zi, gi, f))
             elif kind in ("kpos", "kvel", "kg", "kc2"):
                 kcf[(kind, zi)] = S(n=f"T({gi}, {f})")
-    _emit_outputs(g, xs, copies)
+    _emit_outputs(g, xs, copies if copy_outputs else [])
     if Lo.NK:
         info = []
         for i, K in enumerate(M.kcs):

@@ -10,7 +10,10 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out/cut_$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-for s in 0 7 1 2 4 5 6; do
+# (the overlapped order: 2 = staging, copies and the solve chain alone, 8 =
+# with the early assembly beside the chain; 5 / 6 time the plain order's
+# assembly parts, so those cuts -- and 3 -- run the plain order)
+for s in 0 7 1 2 8 4 5 6; do
     MOCOHIP_IV_DEBUG_STOP=$s timeout -k 10 180 rocprofv3 --kernel-trace --stats --output-format csv \
         -d "$OUT/stop$s" -o run -- python3 "$ROOT/bench.py" --full --steps 50 --warmup 5 --no-cpu-baseline \
         --single-mode --mode fused --intervals "$N" > "$OUT/stop$s.log" 2>&1
