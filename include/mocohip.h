@@ -401,7 +401,49 @@ enum mh_goal_kind {
      * once per finite-difference lane.  mh_batch_* evaluates constraints and
      * their Jacobian only: it accepts contexts with these goals and never
      * reads them, as for every other goal. */
-    MH_GOAL_ORIENTATION_TRACKING = 10
+    MH_GOAL_ORIENTATION_TRACKING = 10,
+    /* (11 is not assigned either: a goal of kind 11 is refused as unknown.) */
+    /* MocoAngularVelocityTrackingGoal (MocoAngularVelocityTrackingGoal.cpp:
+     * 113-161): weight * duration * quadrature over every grid point of
+     *     L(t, q, u) = sum over the tracked frames f, in order, of
+     *                  w_f * |omega_G(frame f; q, u) - ref_f(t)|^2
+     * omega_G = the frame's angular velocity in ground, expressed in ground
+     * (same conditions as kind 7).  Four consecutive terms per frame,
+     * goal_index = the frame's body in all of them (-1 = ground).  Terms 0-2:
+     * goal_column = the table's <frame>/angular_velocity_x / _y / _z column,
+     * goal_weight = 0.0 (unused: an offset frame welded to a body has the
+     * body's angular velocity whatever its location or orientation).  Term 3:
+     * goal_column = -1, goal_weight = w_f (>= 0).  Per frame, each operation
+     * rounded on its own (no fused multiply-add), every 3x3 product entry and
+     * matrix-vector entry summed as (a0 b0 + a1 b1) + a2 b2:
+     *   1. omega = (0, 0, 0) at the ground.
+     *   2. Walk the body's ancestor chain root first.  For each rotation axis a
+     *      of a body, in axis order, whose function is not MH_FN_CONSTANT:
+     *        s     = (R_GF R_cur) dir_a, R_GF = the parent's rotation in ground
+     *                times R_PF and R_cur = the product of the body's earlier
+     *                axis rotations, exactly the matrices the position stage
+     *                holds before it applies axis a's own rotation
+     *        thd   = d1 * u[coord of the function], d1 = the function's first
+     *                derivative (linear: scale * a; spline: scale * s'(q))
+     *        omega_c = omega_c + s_c * thd
+     *      (the angular part of V in the DAE's forward pass).
+     *   3. d_c = omega_c - ref_c(t), s = (d_0 d_0 + d_1 d_1) + d_2 d_2
+     *   4. L += w_f * s                               (from L = 0.0)
+     * For ground omega = 0.  The rounding of R_GF and R_cur themselves is the
+     * position stage's, as for kinds 7, 9 and 10.
+     * Gradient: as kind 7's -- finite-difference quotients of the whole
+     * integrand with k_grad's formulas over t (the t0 / tf entries, seeds 1 - g
+     * and g), over the coordinates on some tracked frame's ancestor chain, and
+     * over every speed whose coordinate is the argument of a non-constant
+     * function on a rotation axis of a body on the chain of a frame tracked by
+     * a goal of this kind.  Written per grid point k: grad[2 + k NS + s] for
+     * those coordinates, grad[2 + k NS + NQ + j] for those speeds, and the
+     * t0 / tf entries; every other entry keeps its bits (speeds that drive
+     * only translation axes or lie off every such chain included).
+     * The goals of this kind share the launch of kinds 7, 9 and 10: a body that
+     * carries an orientation and an angular-velocity item is walked once per
+     * lane. */
+    MH_GOAL_ANGULAR_VELOCITY_TRACKING = 12
 };
 typedef struct mh_goal {
     int32_t kind;

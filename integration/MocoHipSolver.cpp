@@ -32,6 +32,7 @@
 #include <OpenSim/Moco/MocoGoal/MocoInitialActivationGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoMarkerFinalGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoMarkerTrackingGoal.h>
+#include <OpenSim/Moco/MocoGoal/MocoAngularVelocityTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoOrientationTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoTranslationTrackingGoal.h>
 #include <OpenSim/Simulation/StatesTrajectory.h>
@@ -520,29 +521,34 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
             if (std::adjacent_find(sorted.begin(), sorted.end()) == sorted.end())
                 prob.model.add_table(toTable(hg.table, mref.getMarkerTable().flatten(), 5));
         } else if (dynamic_cast<const MocoTranslationTrackingGoal*>(&g) ||
-                   dynamic_cast<const MocoOrientationTrackingGoal*>(&g)) {
+                   dynamic_cast<const MocoOrientationTrackingGoal*>(&g) ||
+                   dynamic_cast<const MocoAngularVelocityTrackingGoal*>(&g)) {
             // The goals keep their splines and an in-memory reference table
             // private, so the frame data is computed again from what is
             // public: the states reference (as initializeOnModelImpl does,
             // MocoOrientationTrackingGoal.cpp:74-109) or the reference file.
             // frame_paths follows the documented behaviour (empty: every
             // column), not the inverted test of the reference's code
-            // (DESIGN.md).  The flattened table -- <path>/position_x|y|z or
-            // <path>/quaternion_e0..3 -- goes in as a model table, splined as
+            // (DESIGN.md).  The flattened table -- <path>/position_x|y|z,
+            // <path>/quaternion_e0..3 or <path>/angular_velocity_x|y|z (the
+            // last realized to the velocity stage, MocoAngularVelocityTracking
+            // Goal.cpp:98-111) -- goes in as a model table, splined as
             // GCVSplineSet(table) does (degree 5); the frames as offset
             // frames with their orientation; mhb::make_rep runs the checks.
             const bool orient = dynamic_cast<const MocoOrientationTrackingGoal*>(&g) != nullptr;
-            hg.kind = orient ? mhb::Goal::ORIENTATION_TRACKING : mhb::Goal::TRANSLATION_TRACKING;
-            hg.table = (orient ? "rotation_reference_" : "translation_reference_") + g.getName();
+            const bool angvel = dynamic_cast<const MocoAngularVelocityTrackingGoal*>(&g) != nullptr;
+            hg.kind = orient ? mhb::Goal::ORIENTATION_TRACKING
+                    : (angvel ? mhb::Goal::ANGULAR_VELOCITY_TRACKING : mhb::Goal::TRANSLATION_TRACKING);
+            const std::string what = orient ? "rotation" : (angvel ? "angular_velocity" : "translation");
+            hg.table = what + "_reference_" + g.getName();
             const auto& pathsProp = g.getPropertyByName("frame_paths");
             std::vector<std::string> paths;
             for (int i = 0; i < pathsProp.size(); ++i) paths.push_back(pathsProp.getValue<std::string>(i));
-            const std::string file = g.getPropertyByName(orient ? "rotation_reference_file"
-                                                                : "translation_reference_file").getValue<std::string>();
+            const std::string file = g.getPropertyByName(what + "_reference_file").getValue<std::string>();
             const auto& statesRef = g.getPropertyByName("states_reference").getValue<TableProcessor>();
             std::vector<double> times;
             std::vector<std::vector<SimTK::Rotation>> rotations;   // [row][frame]
-            std::vector<std::vector<SimTK::Vec3>> positions;
+            std::vector<std::vector<SimTK::Vec3>> positions;       // or angular velocities
             if (!file.empty()) {
                 auto select = [&](const std::vector<std::string>& labels) {
                     if (paths.empty()) paths = labels;
@@ -552,7 +558,7 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
                         OPENSIM_THROW_IF(it == labels.end(), Exception,
                                 "Expected frame_paths to match one of the column labels in the {} reference, but "
                                 "frame path '{}' not found in the reference labels.",
-                                orient ? "rotation" : "translation", path);
+                                orient ? "rotation" : (angvel ? "angular velocity" : "translation"), path);
                         cols.push_back((int)(it - labels.begin()));
                     }
                     return cols;
@@ -584,23 +590,27 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
                 checkLabelsMatchModelStates(model, states.getColumnLabels());
                 auto traj = StatesTrajectory::createFromStatesStorage(model, convertTableToStorage(states));
                 for (auto state : traj) {
-                    model.realizePosition(state);
+                    if (angvel) model.realizeVelocity(state);
+                    else model.realizePosition(state);
                     times.push_back(state.getTime());
                     rotations.emplace_back();
                     positions.emplace_back();
                     for (const auto& path : paths) {
                         const Frame& f = model.getComponent<Frame>(path);
                         rotations.back().push_back(f.getRotationInGround(state));
-                        positions.back().push_back(f.getPositionInGround(state));
+                        positions.back().push_back(angvel ? f.getAngularVelocityInGround(state)
+                                                          : f.getPositionInGround(state));
                     }
                 }
             }
             const int per = orient ? 4 : 3;
             std::vector<std::string> labels;
             static const char* const psfx[3] = {"position_x", "position_y", "position_z"};
+            static const char* const wsfx[3] = {"angular_velocity_x", "angular_velocity_y", "angular_velocity_z"};
             for (const auto& path : paths)
                 for (int c = 0; c < per; ++c)
-                    labels.push_back(orient ? path + "/quaternion_e" + std::to_string(c) : path + "/" + psfx[c]);
+                    labels.push_back(orient ? path + "/quaternion_e" + std::to_string(c)
+                                            : path + "/" + (angvel ? wsfx[c] : psfx[c]));
             TimeSeriesTable flat;
             std::vector<std::string> sorted(paths);
             std::sort(sorted.begin(), sorted.end());
@@ -621,8 +631,7 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
                 }
                 prob.model.add_table(toTable(hg.table, flat, 5));
             }
-            const auto& ws = g.getPropertyByName(orient ? "rotation_weights" : "translation_weights")
-                                     .getValue<MocoWeightSet>();
+            const auto& ws = g.getPropertyByName(what + "_weights").getValue<MocoWeightSet>();
             for (const auto& path : paths) {
                 hg.weights.push_back({path, ws.contains(path) ? ws.get(path).getWeight() : 1.0});
                 if (!model.hasComponent<Frame>(path)) continue;   // make_rep: no frame

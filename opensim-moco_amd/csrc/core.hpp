@@ -2197,10 +2197,11 @@ __device__ __forceinline__ void gather_inputs(const double* __restrict__ x, cons
 }
 
 // Goals that k_marker_tracking evaluates: marker tracking, and the frame
-// tracking goals (translation: position items like markers; orientation).
+// tracking goals (translation: position items like markers; orientation;
+// angular velocity).
 __host__ __device__ __forceinline__ bool goal_tracked_items(int kind) {
     return kind == MH_GOAL_MARKER_TRACKING || kind == MH_GOAL_TRANSLATION_TRACKING ||
-           kind == MH_GOAL_ORIENTATION_TRACKING;
+           kind == MH_GOAL_ORIENTATION_TRACKING || kind == MH_GOAL_ANGULAR_VELOCITY_TRACKING;
 }
 // Goals with an integral (quadrature of an integrand): all but the endpoint
 // costs (final time, final marker) and the marker / frame tracking goals, whose
@@ -2220,7 +2221,7 @@ struct GoalSet {
     const double* gw;
 };
 
-// The tracked items of the marker and frame tracking goals (kinds 7, 9, 10) as
+// The tracked items of the marker and frame tracking goals (kinds 7, 9, 10, 12) as
 // k_marker_tracking reads them: a position item per marker or translation
 // frame (four terms, three reference values), an orientation item per
 // orientation frame (ten terms, four reference values); the items of all such
@@ -2232,8 +2233,20 @@ struct GoalSet {
 // chains' bodies root first; then [nm] the first of each item's terms, [ntg]
 // each goal's index in the GoalSet, [ntg + 1] mbegin, [nlc][nslots] whether
 // lane l's coordinate drives a body of the slot's chain; then [nm] each
-// item's type (0: position, 1: orientation), [nm] the offset of its reference
-// values among a time lane's nref, [nref] the item of each reference value.
+// item's type (0: position, 1: orientation, 2: angular velocity -- kind 12,
+// four terms, three reference values), [nm] the offset of its reference
+// values among a time lane's nref, [nref] the item of each reference value;
+// then the velocity stage's tables: [nslots] the velocity slot of each slot
+// (-1: the slot carries no angular-velocity item, only its pose is computed),
+// [nvs] the slot of each velocity slot, [nq] lane index l of each speed (-1:
+// its coordinate is the argument of no non-constant function on a rotation
+// axis of a body on a velocity slot's chain), [nlu] the speed (coordinate
+// index) of lane l, [nlu][nvs] whether lane l's speed drives such an axis on
+// the velocity slot's chain, [nuw][2] the (lane, velocity slot) pairs for
+// which it does: the walks a speed side costs.
+// Lane order of the kernel in gradient mode: 0 the point; 1 + l coordinate
+// lanes (+h; backward: -h), central also 1 + nlc + l (-h); the 2 or 4 time
+// lanes; then nlu speed lanes (+h; backward: -h), central also nlu more (-h).
 struct MarkerTrack {
     const int* __restrict__ tab;
     int nm;          // tracked items (0: no such goal)
@@ -2243,6 +2256,9 @@ struct MarkerTrack {
     int nq;
     int nchain;      // bodies in all chains
     int nref;        // reference values per time lane (3 or 4 per item)
+    int nvs;         // velocity slots (0: no angular-velocity item)
+    int nlu;         // speeds with lanes
+    int nuw;         // (speed lane, velocity slot) pairs to walk per side
     __device__ __forceinline__ const int* slot() const { return tab; }
     __device__ __forceinline__ const int* chain() const { return tab + nm; }
     __device__ __forceinline__ const int* lane() const { return tab + nm + 2 * nslots; }
@@ -2255,6 +2271,12 @@ struct MarkerTrack {
     __device__ __forceinline__ const int* type() const { return on_chain() + nlc * nslots; }
     __device__ __forceinline__ const int* roff() const { return type() + nm; }
     __device__ __forceinline__ const int* ritem() const { return roff() + nm; }
+    __device__ __forceinline__ const int* vslot() const { return ritem() + nref; }
+    __device__ __forceinline__ const int* vs_slot() const { return vslot() + nslots; }
+    __device__ __forceinline__ const int* ulane() const { return vs_slot() + nvs; }
+    __device__ __forceinline__ const int* ucoord() const { return ulane() + nq; }
+    __device__ __forceinline__ const int* u_on() const { return ucoord() + nlu; }
+    __device__ __forceinline__ const int* uwork() const { return u_on() + nlu * nvs; }
 };
 
 __device__ double goal_integrand(const DevModel& M, const GoalSet& GS, int g, double t,

@@ -411,10 +411,14 @@ __global__ void __launch_bounds__(256) k_reduce_obj(Layout L, GoalSet GS, int mo
 // One step of the position part of dae_eval's forward pass
 // (dae_device.hpp): the parent's pose in ground (Rp, pp) becomes body B's
 // (parent pose x joint frames x coordinate functions).  q: the coordinates,
-// an array or an accessor (QLane).
-template <class Q>
-__device__ __forceinline__ void joint_pose(const DevModel& M, const Q& q, const mh_body& B, double* Rp,
-        double* pp) {
+// an array or an accessor (QLane).  VEL: also the angular part of the
+// velocity stage (the rotation-axis loop of dae_eval; include/mocohip.h
+// MH_GOAL_ANGULAR_VELOCITY_TRACKING): om, the parent's angular velocity in
+// ground, becomes B's at the speeds u (an array or an accessor).  Without
+// VEL the function is the position stage alone, statement for statement.
+template <bool VEL, class Q, class U>
+__device__ __forceinline__ void joint_pose_stage(const DevModel& M, const Q& q, const U& u, const mh_body& B,
+        double* Rp, double* pp, double* om) {
     double RGF[9], t0, t1, t2;
     mm3(Rp, B.R_PF, RGF);
     mv3(Rp, B.p_PF[0], B.p_PF[1], B.p_PF[2], t0, t1, t2);
@@ -435,6 +439,22 @@ __device__ __forceinline__ void joint_pose(const DevModel& M, const Q& q, const 
         if (X.type != MH_AXIS_ROTATION) continue;
         double v, d1, d2;
         fn_eval(M, X.func, q, v, d1, d2);
+        if constexpr (VEL) {
+#pragma clang fp contract(off)
+            const mh_function F = M.funcs[X.func];
+            if (F.kind != MH_FN_CONSTANT) {   // the axis moves with u[F.coord]: s = R_GF R_cur dir
+                double RGc[9];   // every entry (a0 b0 + a1 b1) + a2 b2, as the header states
+                for (int i = 0; i < 3; ++i)
+                    for (int j = 0; j < 3; ++j)
+                        RGc[3 * i + j] = (RGF[3 * i] * Rcur[j] + RGF[3 * i + 1] * Rcur[3 + j]) +
+                                         RGF[3 * i + 2] * Rcur[6 + j];
+                const double s0 = (RGc[0] * X.dir[0] + RGc[1] * X.dir[1]) + RGc[2] * X.dir[2];
+                const double s1 = (RGc[3] * X.dir[0] + RGc[4] * X.dir[1]) + RGc[5] * X.dir[2];
+                const double s2 = (RGc[6] * X.dir[0] + RGc[7] * X.dir[1]) + RGc[8] * X.dir[2];
+                const double thd = d1 * u[F.coord];
+                om[0] = om[0] + s0 * thd; om[1] = om[1] + s1 * thd; om[2] = om[2] + s2 * thd;
+            }
+        }
         double Rk[9];
         axis_rot(X.dir[0], X.dir[1], X.dir[2], v, Rk);
         mm3(Rcur, Rk, Rcur);
@@ -447,6 +467,17 @@ __device__ __forceinline__ void joint_pose(const DevModel& M, const Q& q, const 
                             RGM[3 * i + 2] * B.R_BM[3 * j + 2];
     mv3(Rp, B.p_BM[0], B.p_BM[1], B.p_BM[2], t0, t1, t2);
     pp[0] = oM0 - t0; pp[1] = oM1 - t1; pp[2] = oM2 - t2;
+}
+template <class Q>
+__device__ __forceinline__ void joint_pose(const DevModel& M, const Q& q, const mh_body& B, double* Rp,
+        double* pp) {
+    joint_pose_stage<false>(M, q, q, B, Rp, pp, nullptr);
+}
+// joint_pose and, in om, the body's angular velocity in ground at the speeds u.
+template <class Q, class U>
+__device__ __forceinline__ void joint_pose_velocity(const DevModel& M, const Q& q, const U& u, const mh_body& B,
+        double* Rp, double* pp, double* om) {
+    joint_pose_stage<true>(M, q, u, B, Rp, pp, om);
 }
 
 // Pose of body b in ground at coordinates q, walking b's ancestors from the
@@ -625,28 +656,45 @@ __device__ __forceinline__ double orientation_error_squared(const double* A, con
 
 // The marker and frame tracking goals (MocoMarkerTrackingGoal.cpp:85-107,
 // MocoTranslationTrackingGoal.cpp:137-161, MocoOrientationTrackingGoal.cpp:
-// 169-206; include/mocohip.h MH_GOAL_MARKER_TRACKING to
-// MH_GOAL_ORIENTATION_TRACKING) over their tracked items: a position item per
-// marker or translation frame, an orientation item per orientation frame.
+// 169-206, MocoAngularVelocityTrackingGoal.cpp:113-161; include/mocohip.h
+// MH_GOAL_MARKER_TRACKING to MH_GOAL_ANGULAR_VELOCITY_TRACKING) over their
+// tracked items: a position item per marker or translation frame, an
+// orientation item per orientation frame, an angular-velocity item per
+// angular-velocity frame.
 // Block = grid point k, all of them.  mode 0: the
 // integrand, C[k * ngoals + gi] = quad[k] * L.  mode 1 (gradient) also the
 // finite-difference quotients of the whole integrand with k_grad's formulas
-// and arithmetic, added to what k_grad left in grad's coordinate entries of
-// point k and in tpart[k * 2 + {0, 1}]; every entry has one writer.
+// and arithmetic, added to what k_grad left in grad's coordinate and speed
+// entries of point k and in tpart[k * 2 + {0, 1}]; every entry has one writer.
 // Lanes: 0 the point itself; 1 + l coordinate coord[l] moved by +h (backward
 // differences: -h), central differences also 1 + nlc + l by -h; then the time
 // lanes, t moved by +-h (1 - g) and +-h g in k_grad's order (d = 0, 1; central:
-// the two + lanes, then the two - lanes).  Time lanes move only the reference.
+// the two + lanes, then the two - lanes); last the speed lanes, speed
+// ucoord[l] moved by +h (backward: -h), central also nlu more by -h.  Time
+// lanes move only the reference, speed lanes only the angular velocities.
 // Phase 1: the pose of each distinct body at lane 0 and at every coordinate
 // lane whose coordinate is on the body's chain (MarkerTrack::on_chain; LDS, 12
-// doubles), and the
-// reference of every item (three positions or four quaternion values) at the
-// base and the time lanes' times.
-// Phase 2: thread = (lane, item): the squared distance or squared angle, from
-// the lane's pose where phase 1 wrote one and lane 0's otherwise -- an item
-// off the perturbed chain gives both sides of the quotient the same bits.
+// doubles); for a slot that carries an angular-velocity item (a velocity
+// slot) the same walk also leaves the body's angular velocity (LDS, 3
+// doubles, in an array of its own: the pose records keep their layout), and
+// one more walk per speed side and (speed lane, velocity slot) pair whose
+// speed drives a rotation axis of the slot's chain leaves that lane's; and
+// the reference of every item (three values, or four quaternion values) at
+// the base and the time lanes' times.
+// Phase 2: thread = (lane, item): the squared distance, angle or rate
+// difference, from the lane's pose / angular velocity where phase 1 wrote one
+// and lane 0's otherwise -- an item off the perturbed chain gives both sides
+// of the quotient the same bits.  Position and orientation items have no
+// value of their own in a speed lane: phase 3 takes lane 0's.
 // Phase 3: thread = (lane, goal) sums the goal's items in order; then
-// thread = direction forms the quotients.
+// thread = direction (2 + nlc + nlu of them) forms the quotients.
+// VEL = false: the kernel for problems without an angular-velocity item -- no
+// velocity slot, no speed lane, the statements of the kernel before the
+// velocity stage; the host launches it for problems without a goal of kind
+// MH_GOAL_ANGULAR_VELOCITY_TRACKING, so the stage costs them nothing.  A goal
+// whose frames all sit on ground has items of type 2 and no velocity slot:
+// it runs the VEL = true kernel, which reads omega = 0 for them.
+template <bool VEL>
 __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, GoalSet GS, MarkerTrack T, int fd,
         double h, int mode, const double* __restrict__ x, const double* __restrict__ grid,
         const double* __restrict__ quad, double* __restrict__ C, double* __restrict__ grad,
@@ -658,29 +706,76 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
     const int sides = fd == MH_FD_CENTRAL ? 2 : 1;
     const int npl = 1 + (mode ? sides * nlc : 0);   // lanes with poses of their own
     const int nt = mode ? 2 * sides : 0;            // time lanes
-    const int nl = npl + nt;
+    const int nvs = VEL ? T.nvs : 0, nlu = VEL ? T.nlu : 0;
+    const int nu = mode ? sides * nlu : 0;          // speed lanes
+    const int nl = npl + nt + nu;
     double* pose = mt_lds;                          // [npl][slot][12]
     double* ref = pose + (long)npl * ns * 12;       // [1 + nt][nref]: item m's from roff[m]
     double* sq = ref + (long)(1 + nt) * nref;       // [lane][item]
     double* Lv = sq + (long)nl * nm;                // [lane][goal]
     const double g = grid[k], dur = x[1] - x[0], t = dur * g + x[0];
     const double* q = x + 2 + (long)k * L.NS;
-    for (int w = threadIdx.x; w < npl * ns; w += blockDim.x) {
-        const int pl = w / ns, sl = w - pl * ns;
-        QLane Q{q, -1, 0.0};
-        if (pl > 0) {
-            const int l = (pl - 1) % nlc;
-            if (!T.on_chain()[l * ns + sl]) continue;   // phase 2 reads lane 0's pose
-            Q.s = T.coord()[l];
-            Q.d = fd == MH_FD_BACKWARD || pl > nlc ? -h : h;
+    if constexpr (VEL) {
+        double* om = Lv + (long)nl * ntg;           // [npl + nu][velocity slot][3]
+        const int nuw = mode ? sides * T.nuw : 0;   // the speed lanes' walks
+        for (int w = threadIdx.x; w < npl * ns + nuw; w += blockDim.x) {
+            QLane Q{q, -1, 0.0}, U{q + L.NQ, -1, 0.0};
+            int sl, vs;
+            double *o = nullptr, *ow = nullptr;
+            if (w < npl * ns) {
+                const int pl = w / ns;
+                sl = w - pl * ns;
+                if (pl > 0) {
+                    const int l = (pl - 1) % nlc;
+                    if (!T.on_chain()[l * ns + sl]) continue;   // phase 2 reads lane 0's pose
+                    Q.s = T.coord()[l];
+                    Q.d = fd == MH_FD_BACKWARD || pl > nlc ? -h : h;
+                }
+                o = pose + (long)w * 12;
+                vs = T.vslot()[sl];
+                if (vs >= 0) ow = om + ((long)pl * nvs + vs) * 3;
+            } else {
+                const int i = w - npl * ns, side = i / T.nuw, r = i - side * T.nuw;
+                const int l = T.uwork()[2 * r];
+                vs = T.uwork()[2 * r + 1];
+                sl = T.vs_slot()[vs];
+                U.s = T.ucoord()[l];
+                U.d = fd == MH_FD_BACKWARD || side ? -h : h;
+                ow = om + ((long)(npl + side * nlu + l) * nvs + vs) * 3;
+            }
+            const int cb = T.chain()[2 * sl], cn = T.chain()[2 * sl + 1];
+            const int* bodies = T.bodies() + cb;
+            double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
+            if (vs < 0) {
+                for (int ci = 0; ci < cn; ++ci) joint_pose(M, Q, M.bodies[bodies[ci]], R, p);
+            } else {
+                double wv[3] = {0, 0, 0};
+                for (int ci = 0; ci < cn; ++ci) joint_pose_velocity(M, Q, U, M.bodies[bodies[ci]], R, p, wv);
+                for (int i = 0; i < 3; ++i) ow[i] = wv[i];
+            }
+            if (o) {
+                for (int i = 0; i < 9; ++i) o[i] = R[i];
+                for (int i = 0; i < 3; ++i) o[9 + i] = p[i];
+            }
         }
-        const int cb = T.chain()[2 * sl], cn = T.chain()[2 * sl + 1];
-        const int* bodies = T.bodies() + cb;
-        double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
-        for (int ci = 0; ci < cn; ++ci) joint_pose(M, Q, M.bodies[bodies[ci]], R, p);
-        double* o = pose + (long)w * 12;
-        for (int i = 0; i < 9; ++i) o[i] = R[i];
-        for (int i = 0; i < 3; ++i) o[9 + i] = p[i];
+    } else {
+        for (int w = threadIdx.x; w < npl * ns; w += blockDim.x) {
+            const int pl = w / ns, sl = w - pl * ns;
+            QLane Q{q, -1, 0.0};
+            if (pl > 0) {
+                const int l = (pl - 1) % nlc;
+                if (!T.on_chain()[l * ns + sl]) continue;   // phase 2 reads lane 0's pose
+                Q.s = T.coord()[l];
+                Q.d = fd == MH_FD_BACKWARD || pl > nlc ? -h : h;
+            }
+            const int cb = T.chain()[2 * sl], cn = T.chain()[2 * sl + 1];
+            const int* bodies = T.bodies() + cb;
+            double R[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1}, p[3] = {0, 0, 0};
+            for (int ci = 0; ci < cn; ++ci) joint_pose(M, Q, M.bodies[bodies[ci]], R, p);
+            double* o = pose + (long)w * 12;
+            for (int i = 0; i < 9; ++i) o[i] = R[i];
+            for (int i = 0; i < 3; ++i) o[9 + i] = p[i];
+        }
     }
     for (int w = threadIdx.x; w < (1 + nt) * nref; w += blockDim.x) {
         const int tl = w / nref, r = w - tl * nref, m = T.ritem()[r], c = r - T.roff()[m];
@@ -698,9 +793,32 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
     __syncthreads();
     for (int w = threadIdx.x; w < nl * nm; w += blockDim.x) {
         const int ln = w / nm, m = w - ln * nm;
-        const int tl = ln < npl ? 0 : ln - npl + 1;
+        int tl = ln < npl ? 0 : ln - npl + 1;
         const int sl = T.slot()[m];
         const double* w3 = GS.gw + T.term()[m];
+        if constexpr (VEL) {
+            if (ln >= npl + nt) tl = 0;   // a speed lane: the base time
+            if (T.type()[m] == 2) {       // angular velocity: three reference values
+                double w0 = 0.0, w1 = 0.0, w2 = 0.0;
+                if (sl >= 0) {
+                    const double* om = Lv + (long)nl * ntg;
+                    const int vs = T.vslot()[sl];
+                    int rec = 0;   // lane 0's unless phase 1 wrote this lane's
+                    if (ln < npl) {
+                        if (ln > 0 && T.on_chain()[(ln - 1) % nlc * ns + sl]) rec = ln;
+                    } else if (ln >= npl + nt) {
+                        if (T.u_on()[(ln - npl - nt) % nlu * nvs + vs]) rec = ln - nt;
+                    }
+                    const double* A = om + ((long)rec * nvs + vs) * 3;
+                    w0 = A[0]; w1 = A[1]; w2 = A[2];
+                }
+                const double* rf = ref + (long)tl * nref + T.roff()[m];
+                const double d0 = w0 - rf[0], d1 = w1 - rf[1], d2 = w2 - rf[2];
+                sq[w] = (d0 * d0 + d1 * d1) + d2 * d2;
+                continue;
+            }
+            if (ln >= npl + nt) continue;   // a speed lane: phase 3 takes lane 0's value
+        }
         if (T.type()[m]) {   // orientation: R_BO in w3[0..9), four reference values
             const double* A = nullptr;
             if (sl >= 0) {
@@ -728,16 +846,27 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
     for (int w = threadIdx.x; w < nl * ntg; w += blockDim.x) {
         const int ln = w / ntg, j = w - ln * ntg;
         double s = 0.0;
-        for (int m = T.mbegin()[j]; m < T.mbegin()[j + 1]; ++m)
-            s += GS.gw[T.term()[m] + (T.type()[m] ? 9 : 3)] * sq[(long)ln * nm + m];
+        if constexpr (VEL) {
+            for (int m = T.mbegin()[j]; m < T.mbegin()[j + 1]; ++m) {
+                const int type = T.type()[m];
+                const int lv = type != 2 && ln >= npl + nt ? 0 : ln;   // speed lanes move only type 2
+                s += GS.gw[T.term()[m] + (type == 1 ? 9 : 3)] * sq[(long)lv * nm + m];
+            }
+        } else {
+            for (int m = T.mbegin()[j]; m < T.mbegin()[j + 1]; ++m)
+                s += GS.gw[T.term()[m] + (T.type()[m] ? 9 : 3)] * sq[(long)ln * nm + m];
+        }
         Lv[w] = s;
     }
     __syncthreads();
     for (int j = threadIdx.x; j < ntg; j += blockDim.x) C[(long)k * GS.ngoals + T.goal()[j]] = quad[k] * Lv[j];
     if (!mode) return;
-    for (int d = threadIdx.x; d < 2 + nlc; d += blockDim.x) {
-        const int la = d < 2 ? npl + d : 1 + (d - 2);             // +h (backward: -h)
-        const int lb = d < 2 ? npl + 2 + d : 1 + nlc + (d - 2);   // -h, central only
+    for (int d = threadIdx.x; d < 2 + nlc + nlu; d += blockDim.x) {
+        int la = d < 2 ? npl + d : 1 + (d - 2);             // +h (backward: -h)
+        int lb = d < 2 ? npl + 2 + d : 1 + nlc + (d - 2);   // -h, central only
+        if constexpr (VEL) {
+            if (d >= 2 + nlc) { la = npl + nt + (d - 2 - nlc); lb = la + nlu; }   // a speed
+        }
         double acc = 0.0;
         for (int j = 0; j < ntg; ++j) {
             const mh_goal G = GS.goals[T.goal()[j]];
@@ -747,7 +876,8 @@ __global__ void __launch_bounds__(128) k_marker_tracking(DevModel M, Layout L, G
             acc += G.weight * dur * quad[k] * dL;
         }
         if (d < 2) tpart[(long)k * 2 + d] += acc;
-        else grad[2 + (long)k * L.NS + T.coord()[d - 2]] += acc;
+        else if (!VEL || d < 2 + nlc) grad[2 + (long)k * L.NS + T.coord()[d - 2]] += acc;
+        else grad[2 + (long)k * L.NS + L.NQ + T.ucoord()[d - 2 - nlc]] += acc;
     }
 }
 
@@ -1794,7 +1924,7 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
     // (a bad index would be an out-of-bounds device read)
     for (int g = 0; g < p->ngoals; ++g) {
         const mh_goal& G = p->goals[g];
-        // tracked items (kinds 7, 9, 10): tn terms each, the last one the weight
+        // tracked items (kinds 7, 9, 10, 12): tn terms each, the last one the weight
         const bool tracking = goal_tracked_items(G.kind);
         const int tn = G.kind == MH_GOAL_ORIENTATION_TRACKING ? 10 : 4;
         const int tcols = G.kind == MH_GOAL_ORIENTATION_TRACKING ? 4 : 3;   // leading terms with a column
@@ -1817,7 +1947,7 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
             case MH_GOAL_STATE_TRACKING: case MH_GOAL_SUM_SQUARED_STATE: hi = c->NS; break;
             case MH_GOAL_AUX_DERIVATIVES: hi = c->NAR; break;
             case MH_GOAL_MARKER_FINAL: case MH_GOAL_MARKER_TRACKING: case MH_GOAL_TRANSLATION_TRACKING:
-            case MH_GOAL_ORIENTATION_TRACKING: hi = M.nbodies; break;
+            case MH_GOAL_ORIENTATION_TRACKING: case MH_GOAL_ANGULAR_VELOCITY_TRACKING: hi = M.nbodies; break;
             default: hi = INT32_MAX; break;   // final time: no terms read
             }
             if (idx < (marker ? -1 : 0) || idx >= hi)
@@ -2073,7 +2203,7 @@ static MarkerTrack marker_tracking_tables(mh_ctx* c, const mh_model& M, const st
         mbegin.push_back((int)term.size());
         for (int k = G.term_begin; k < G.term_begin + G.term_count; k += orient ? 10 : 4) {
             ref_body.push_back(c->gidx[k]);
-            type.push_back(orient);
+            type.push_back(orient ? 1 : (G.kind == MH_GOAL_ANGULAR_VELOCITY_TRACKING ? 2 : 0));
             roff.push_back((int)ritem.size());
             ritem.insert(ritem.end(), orient ? 4 : 3, (int)term.size());
             term.push_back(k);
@@ -2106,10 +2236,47 @@ static MarkerTrack marker_tracking_tables(mh_ctx* c, const mh_model& M, const st
     c->mt_tab.insert(c->mt_tab.end(), type.begin(), type.end());
     c->mt_tab.insert(c->mt_tab.end(), roff.begin(), roff.end());
     c->mt_tab.insert(c->mt_tab.end(), ritem.begin(), ritem.end());
+    // the velocity stage: the slots with an angular-velocity item, and the
+    // speeds whose coordinate moves a rotation axis (a non-constant function)
+    // of a body on such a slot's chain
+    const int* slot = B.tab.data();
+    std::vector<int> vslot(T.nslots, -1), vs_slot;
+    for (int m = 0; m < T.nm; ++m)
+        if (type[m] == 2 && slot[m] >= 0 && vslot[slot[m]] < 0) {
+            vslot[slot[m]] = (int)vs_slot.size();
+            vs_slot.push_back(slot[m]);
+        }
+    T.nvs = (int)vs_slot.size();
+    auto drives = [&](int j, int sl) {   // speed j, slot sl
+        const int* cb = bodies + chain[2 * sl];
+        for (int ci = 0; ci < chain[2 * sl + 1]; ++ci) {
+            const mh_body& Bd = M.bodies[cb[ci]];
+            for (int a = Bd.axis_begin; a < Bd.axis_begin + Bd.axis_count; ++a) {
+                const mh_function& F = M.functions[M.axes[a].func];
+                if (M.axes[a].type == MH_AXIS_ROTATION && F.kind != MH_FN_CONSTANT && F.coord == j) return true;
+            }
+        }
+        return false;
+    };
+    std::vector<int> ulane(M.nq, -1), ucoord, u_on, uwork;
+    for (int j = 0; j < M.nq; ++j)
+        for (int sl : vs_slot)
+            if (drives(j, sl)) { ulane[j] = (int)ucoord.size(); ucoord.push_back(j); break; }
+    T.nlu = (int)ucoord.size();
+    for (int l = 0; l < T.nlu; ++l)
+        for (int vs = 0; vs < T.nvs; ++vs) {
+            u_on.push_back(drives(ucoord[l], vs_slot[vs]));
+            if (u_on.back()) { uwork.push_back(l); uwork.push_back(vs); }
+        }
+    T.nuw = (int)uwork.size() / 2;
+    for (const std::vector<int>* v : {&vslot, &vs_slot, &ulane, &ucoord, &u_on, &uwork})
+        c->mt_tab.insert(c->mt_tab.end(), v->begin(), v->end());
     const size_t sides = c->fd == MH_FD_CENTRAL ? 2 : 1;
     for (int mode = 0; mode < 2; ++mode) {
-        const size_t npl = 1 + (mode ? sides * T.nlc : 0), nt = mode ? 2 * sides : 0, nl = npl + nt;
-        c->mt_lds[mode] = sizeof(double) * (12 * npl * T.nslots + (1 + nt) * T.nref + nl * T.nm + nl * T.ntg);
+        const size_t npl = 1 + (mode ? sides * T.nlc : 0), nt = mode ? 2 * sides : 0,
+                     nu = mode ? sides * T.nlu : 0, nl = npl + nt + nu;
+        c->mt_lds[mode] = sizeof(double) * (12 * npl * T.nslots + (1 + nt) * T.nref + nl * T.nm + nl * T.ntg +
+                                            3 * (npl + nu) * T.nvs);
     }
     return T;
 }
@@ -2124,7 +2291,8 @@ static int kinematics_tables(mh_ctx* c, const mh_model& M, const std::vector<int
     MT = marker_tracking_tables(c, M, coord_body);
     if (c->mt_lds[1] > 64 * 1024)
         return set_err(MH_ERR_UNSUPPORTED, "marker tracking: %d tracked items on %d bodies x %d coordinate lanes "
-                       "exceed the LDS", MT.nm, MT.nslots, MT.nlc);
+                       "(%d velocity slots, %d speed lanes) exceed the LDS", MT.nm, MT.nslots, MT.nlc, MT.nvs,
+                       MT.nlu);
     return MH_OK;
 }
 
@@ -3508,8 +3676,12 @@ extern "C" int mh_eval_g_jac_g(mh_ctx* c, const double* x, double* g, double* va
 // at during the call (the shard's, for a partial).
 static void launch_marker_tracking(mh_ctx* c, const Layout& L, int mode) {
     if (c->MT.nm == 0) return;
-    hipLaunchKernelGGL(k_marker_tracking, dim3((unsigned)c->G), dim3(128), c->mt_lds[mode], c->stream, c->M, L,
-            c->GS, c->MT, c->fd, c->h, mode, c->d_x, c->d_grid, c->d_quad, c->d_C, c->d_grad, c->d_tpart);
+    // (no angular-velocity goal, hence no item of type 2: the instantiation without the velocity stage)
+    bool vel = false;
+    for (const mh_goal& G : c->goals) vel = vel || G.kind == MH_GOAL_ANGULAR_VELOCITY_TRACKING;
+    hipLaunchKernelGGL(vel ? k_marker_tracking<true> : k_marker_tracking<false>, dim3((unsigned)c->G),
+            dim3(128), c->mt_lds[mode], c->stream, c->M, L, c->GS, c->MT, c->fd, c->h, mode, c->d_x, c->d_grid,
+            c->d_quad, c->d_C, c->d_grad, c->d_tpart);
 }
 
 // The objective (partial = false) or this shard's partial of it (partial =

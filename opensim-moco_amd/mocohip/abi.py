@@ -22,6 +22,7 @@ MH_GOAL_CONTROL, MH_GOAL_STATE_TRACKING, MH_GOAL_FINAL_TIME, \
     MH_GOAL_SUM_SQUARED_STATE, MH_GOAL_AUX_DERIVATIVES, MH_GOAL_MARKER_FINAL = 0, 1, 2, 3, 4, 5
 MH_GOAL_MARKER_TRACKING = 7   # 6: the library's own multiplier term
 MH_GOAL_TRANSLATION_TRACKING, MH_GOAL_ORIENTATION_TRACKING = 9, 10   # 8: not assigned
+MH_GOAL_ANGULAR_VELOCITY_TRACKING = 12   # 11: not assigned
 MH_HERMITE_SIMPSON, MH_TRAPEZOIDAL = 0, 1
 MH_DYNAMICS_EXPLICIT, MH_DYNAMICS_IMPLICIT = 0, 1
 MH_FD_CENTRAL, MH_FD_FORWARD, MH_FD_BACKWARD = 0, 1, 2

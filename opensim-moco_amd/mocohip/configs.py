@@ -21,14 +21,14 @@ from typing import Optional
 
 import numpy as np
 
-from .model import (Body, Coordinate, CoordinateActuator, DataTable,
-                    ExternalForce, Joint, Marker, Model, SpringGeneralizedForce, model_from_dict)
+from .model import (Axis, Body, Coordinate, CoordinateActuator, DataTable,
+                    ExternalForce, Function, Joint, Marker, Model, SpringGeneralizedForce, model_from_dict)
 from . import abi
 from .osim import add_reserves
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm,
                       MocoControlBoundConstraint, MocoControlGoal, MocoFrameDistanceConstraint,
                       MocoInitialActivationGoal,
-                      FrameReference, MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoMarkerTrackingGoal,
+                      FrameReference, MocoAngularVelocityTrackingGoal, MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoMarkerTrackingGoal,
                       MarkersReference, MocoOrientationTrackingGoal, MocoProblem, MocoStateTrackingGoal,
                       MocoTranslationTrackingGoal, PiecewiseLinearFunction)
 from .solver import MocoHipSolver, MocoStudy
@@ -594,7 +594,8 @@ def double_pendulum_frame_tracking(kind: str = "orientation", reference_solution
                                    fd_scheme: str = "central") -> MocoStudy:
     """testMocoGoals.cpp:234-256 (testDoublePendulumTracking): the effort
     problem with the effort goal's weight 0.001 and a tracking goal "tracking"
-    of ``kind`` ("translation" / "orientation") on the frames /bodyset/b0 and
+    of ``kind`` ("translation" / "orientation" / "angular_velocity"; the last:
+    testMocoGoals.cpp:319-325) on the frames /bodyset/b0 and
     /bodyset/b1, its states reference the effort solution (a MocoTrajectory or
     a states DataTable; None: double_pendulum_swing_states)."""
     st = double_pendulum_effort(num_mesh_intervals, scheme, effort_weight=0.001)
@@ -603,7 +604,8 @@ def double_pendulum_frame_tracking(kind: str = "orientation", reference_solution
         reference_solution = double_pendulum_swing_states()
     elif not isinstance(reference_solution, DataTable):
         reference_solution = states_table(reference_solution)
-    cls = {"translation": MocoTranslationTrackingGoal, "orientation": MocoOrientationTrackingGoal}[kind]
+    cls = {"translation": MocoTranslationTrackingGoal, "orientation": MocoOrientationTrackingGoal,
+           "angular_velocity": MocoAngularVelocityTrackingGoal}[kind]
     g = cls("tracking", 1.0, states_reference=reference_solution, frame_paths=["/bodyset/b0", "/bodyset/b1"])
     st.problem.model.add_table(g.reference_table(st.problem.model))
     st.problem.add_goal(g)
@@ -616,14 +618,23 @@ def gimbal_motion(times):
     return {"qx": 0.6 * np.sin(2.0 * t + 0.3), "qy": 0.7 * np.cos(3.0 * t), "qz": -0.5 + 0.8 * t}
 
 
+def gimbal_motion_rates(times):
+    """d/dt of gimbal_motion."""
+    t = np.asarray(times, float)
+    return {"qx": 1.2 * np.cos(2.0 * t + 0.3), "qy": -2.1 * np.sin(3.0 * t), "qz": 0.8 + 0.0 * t}
+
+
 def gimbal_frame_tracking(num_mesh_intervals: int = 2, scheme: str = "hermite-simpson",
-                          fd_scheme: str = "central") -> MocoStudy:
+                          fd_scheme: str = "central", angular_velocity: bool = False) -> MocoStudy:
     """gimbal_frame_distance's model (a body on a GimbalJoint) with a rotated
     offset frame "sensor" on the body (translation (-0.5, 0.1, 0.2),
     orientation (0.4, -0.7, 1.1)): orientation tracking of the sensor (weight
     2) and of the body frame, translation tracking of the sensor (weight 3),
     the references given as tables computed along gimbal_motion at 26 rows,
-    plus a control-effort goal (0.001)."""
+    plus a control-effort goal (0.001).  ``angular_velocity``: also a
+    MocoAngularVelocityTrackingGoal "angular_velocity_tracking" (weight 0.25)
+    of the sensor (weight 1.5) after the other two, its reference the sensor's
+    angular velocity along the same motion."""
     m = gimbal_frame_distance(num_mesh_intervals).problem.model
     m.add_offset_frame("sensor", "body", (-0.5, 0.1, 0.2), (0.4, -0.7, 1.1))
     sensor = "/bodyset/body/sensor"
@@ -642,7 +653,16 @@ def gimbal_frame_tracking(num_mesh_intervals: int = 2, scheme: str = "hermite-si
     for n in ("qx", "qy", "qz"):
         p.set_state_info(f"/jointset/gimbal/{n}/value", (-third, third))
         p.set_state_info(f"/jointset/gimbal/{n}/speed", (-10, 10))
-    for g in (go, gt):
+    goals = [go, gt]
+    if angular_velocity:
+        rate = gimbal_motion_rates(times)
+        om = [[m.frame_angular_velocity_in_ground(sensor, {n: v[r] for n, v in mot.items()},
+                                                  {n: v[r] for n, v in rate.items()})]
+              for r in range(len(times))]
+        goals.append(MocoAngularVelocityTrackingGoal("angular_velocity_tracking", 0.25,
+                                                     reference=FrameReference(times, [sensor], np.array(om)),
+                                                     frame_weights={sensor: 1.5}))
+    for g in goals:
         m.add_table(g.reference_table(m))
         p.add_goal(g)
     p.add_goal(MocoControlGoal("control_effort", 0.001))
@@ -693,6 +713,128 @@ def gait10dof18musc_frame_track_few(num_mesh_intervals: int = 3, **kw) -> MocoSt
     launch."""
     return gait10dof18musc_frame_track(num_mesh_intervals, markers=(GAIT_MARKERS_FEW[0], GAIT_MARKERS_FEW[2]),
                                        frames=GAIT_ORIENTATION_FRAMES_FEW, translation=True, **kw)
+
+
+def append_value_derivatives_as_speeds(states: DataTable, degree: int = 5) -> DataTable:
+    """TableProcessor's appendCoordinateValueDerivativesAsSpeeds (what
+    MocoTrack's track_reference_position_derivatives does): for every
+    <coordinate>/value column without a <coordinate>/speed column, the speed
+    is the derivative at the rows of the column's interpolating spline."""
+    from .splines import gcv_interpolating_ppoly
+    t = np.asarray(states.times, float)
+    cols = dict(states.columns)
+    for k, v in states.columns.items():
+        sp = k[:-len("value")] + "speed"
+        if not k.endswith("/value") or sp in cols:
+            continue
+        br, cf = gcv_interpolating_ppoly(t, np.asarray(v, float), degree)
+        dt = br[-1] - br[-2]
+        last = sum(n * cf[-1, 0, n] * dt ** (n - 1) for n in range(1, degree + 1))
+        cols[sp] = np.append(cf[:, 0, 1], last)
+    return DataTable(states.name, t, cols)
+
+
+def gait10dof18musc_imu_track(num_mesh_intervals: int = 200, frames=GAIT_ORIENTATION_FRAMES,
+                              **kw) -> MocoStudy:
+    """gait10dof18musc_frame_track plus a MocoAngularVelocityTrackingGoal
+    "angular_velocity_tracking" (weight 1, frame weights 1) on the same
+    ``frames`` -- an inertial sensor's orientation and gyroscope rate per
+    segment, one kinematics pass for both; the reference is computed from the
+    bundled walking data's coordinate values and their derivatives as speeds
+    (append_value_derivatives_as_speeds: the data has values only)."""
+    st = gait10dof18musc_frame_track(num_mesh_intervals, frames=frames, **kw)
+    m = st.problem.model
+    data = _load("walk_gait1018_state_reference.json")
+    states = DataTable("states_reference", np.asarray(data["time"]),
+                       {k: np.asarray(v, float) for k, v in data["columns"].items()})
+    g = MocoAngularVelocityTrackingGoal("angular_velocity_tracking", 1.0,
+                                        states_reference=append_value_derivatives_as_speeds(states),
+                                        frame_paths=list(frames))
+    m.add_table(g.reference_table(m))
+    st.problem.goals.insert(len(st.problem.goals) - 1, g)   # before the effort goal
+    return st
+
+
+def gait10dof18musc_imu_track_few(num_mesh_intervals: int = 3, **kw) -> MocoStudy:
+    """N = 3: gait10dof18musc_frame_track_few plus angular-velocity tracking
+    of the pelvis, both femurs and both tibias."""
+    return gait10dof18musc_imu_track(num_mesh_intervals, markers=(GAIT_MARKERS_FEW[0], GAIT_MARKERS_FEW[2]),
+                                     frames=GAIT_ORIENTATION_FRAMES_FEW, translation=True, **kw)
+
+
+def spline_knee_model(slider_foot: bool = False) -> Model:
+    """A thigh on a pin joint and a shank on a custom joint with one
+    coordinate, knee, that drives -- in this axis order -- a rotation about z
+    through a SimmSpline (seven knots, slope from 0.4 to 1.6), a rotation about
+    x through a linear function (0.3 knee) and a translation along y through a
+    SimmSpline: the coupled knee of a gait model, small.  CoordinateActuators
+    on both coordinates, an offset frame "imu" on the shank.  ``slider_foot``:
+    also a foot on a slider joint under the shank, whose coordinate turns
+    nothing."""
+    m = Model("spline_knee")
+    m.add_body(Body("thigh", 2.0, (0, -0.2, 0), (0.1, 0.02, 0.1, 0, 0, 0)))
+    m.add_body(Body("shank", 1.5, (0, -0.2, 0), (0.08, 0.01, 0.08, 0, 0, 0)))
+    hip = Coordinate("hip", (-1.5, 1.5))
+    knee = Coordinate("knee", (-2.0, 0.2))
+    m.add_joint(Joint.pin("hip", "ground", "thigh", hip, loc_in_parent=(0, 1, 0)))
+    kx = (-2.0, -1.6, -1.2, -0.8, -0.4, 0.0, 0.2)
+    m.add_joint(Joint("knee", "thigh", "shank", [knee], [
+        Axis(abi.MH_AXIS_ROTATION, (0, 0, 1),
+             Function.simm_spline("knee", kx, (-2.32, -2.08, -1.72, -1.24, -0.66, 0.0, 0.32))),
+        Axis(abi.MH_AXIS_ROTATION, (1, 0, 0), Function.linear("knee", 0.3)),
+        Axis(abi.MH_AXIS_TRANSLATION, (0, 1, 0),
+             Function.simm_spline("knee", kx, (-0.422, -0.4082, -0.399, -0.3976, -0.3966, -0.3952, -0.3946))),
+    ], loc_in_parent=(0, -0.05, 0)))
+    m.add_coordinate_actuator(CoordinateActuator("tau_hip", "hip", 10.0, path="/tau_hip"))
+    m.add_coordinate_actuator(CoordinateActuator("tau_knee", "knee", 10.0, path="/tau_knee"))
+    m.add_offset_frame("imu", "shank", (0.03, -0.15, 0.02), (0.2, 0.5, -0.4))
+    if slider_foot:
+        m.add_body(Body("foot", 0.5, (0.05, 0, 0), (0.01, 0.01, 0.01, 0, 0, 0)))
+        slide = Coordinate("slide", (-0.1, 0.1), motion_type="translational")
+        m.add_joint(Joint.slider("ankle", "shank", "foot", slide, loc_in_parent=(0, -0.4, 0)))
+        m.add_coordinate_actuator(CoordinateActuator("tau_slide", "slide", 10.0, path="/tau_slide"))
+    return m
+
+
+def spline_knee_motion(times):
+    """A smooth motion of (hip, knee) within their ranges, and its rates."""
+    t = np.asarray(times, float)
+    return ({"hip": 0.5 * np.sin(3.0 * t), "knee": -0.9 + 0.8 * np.cos(2.0 * t + 0.4)},
+            {"hip": 1.5 * np.cos(3.0 * t), "knee": -1.6 * np.sin(2.0 * t + 0.4)})
+
+
+def spline_knee(num_mesh_intervals: int = 2, scheme: str = "hermite-simpson", fd_scheme: str = "central",
+                slider_foot: bool = False) -> MocoStudy:
+    """spline_knee_model over [0, 0.6]: a MocoAngularVelocityTrackingGoal of
+    the thigh, of the shank's "imu" frame (weight 2) and, with ``slider_foot``,
+    of the foot, the reference computed along spline_knee_motion at 31 rows,
+    plus a control-effort goal (0.001).  No generated back end: the device
+    interpreter runs it."""
+    m = spline_knee_model(slider_foot)
+    imu = "/bodyset/shank/imu"
+    paths = ["/bodyset/thigh", imu] + (["/bodyset/foot"] if slider_foot else [])
+    times = np.linspace(0.0, 0.6, 31)
+    q, u = spline_knee_motion(times)
+    om = [[m.frame_angular_velocity_in_ground(f, {n: v[r] for n, v in q.items()}, {n: v[r] for n, v in u.items()})
+           for f in paths] for r in range(len(times))]
+    g = MocoAngularVelocityTrackingGoal("angular_velocity_tracking", 1.0,
+                                        reference=FrameReference(times, paths, np.array(om)),
+                                        frame_weights={imu: 2.0})
+    m.add_table(g.reference_table(m))
+    p = MocoProblem(m)
+    p.set_time_bounds(0, 0.6)
+    p.set_state_info("/jointset/hip/hip/value", (-1.5, 1.5))
+    p.set_state_info("/jointset/hip/hip/speed", (-10, 10))
+    p.set_state_info("/jointset/knee/knee/value", (-2.0, 0.2))
+    p.set_state_info("/jointset/knee/knee/speed", (-10, 10))
+    if slider_foot:
+        p.set_state_info("/jointset/ankle/slide/value", (-0.1, 0.1))
+        p.set_state_info("/jointset/ankle/slide/speed", (-1, 1))
+    p.add_goal(g)
+    p.add_goal(MocoControlGoal("control_effort", 0.001))
+    s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals, transcription_scheme=scheme,
+                      optim_finite_difference_scheme=fd_scheme)
+    return MocoStudy(p, s)
 
 
 def scale_subject(m: Model, length: float = 1.03, mass: float = 1.05) -> Model:
@@ -967,6 +1109,9 @@ CONFIGS = {
     "gimbal_frame_tracking": gimbal_frame_tracking,
     "gait10dof18musc_frame_track": gait10dof18musc_frame_track,
     "gait10dof18musc_frame_track_few": gait10dof18musc_frame_track_few,
+    "gait10dof18musc_imu_track": gait10dof18musc_imu_track,
+    "gait10dof18musc_imu_track_few": gait10dof18musc_imu_track_few,
+    "spline_knee": spline_knee,
     "wrapped_pendulum": wrapped_pendulum,
     "rajagopal18_inverse": rajagopal18_inverse,
     "rajagopal80": rajagopal80,

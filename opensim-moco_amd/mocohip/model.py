@@ -479,6 +479,52 @@ class Model:
         X = self._body_transforms_in_ground(coordinates)[fr[0]]
         return (X @ np.append(np.asarray(fr[1], float), 1.0))[:3], X[:3, :3] @ self.find_frame_orientation(path)
 
+    def frame_angular_velocity_in_ground(self, path: str, coordinates: Dict[str, float],
+                                         speeds: Dict[str, float]) -> np.ndarray:
+        """The angular velocity in ground, expressed in ground, of the Frame
+        at ``path`` at the given coordinate values and speeds (both by
+        coordinate name; a missing speed is 0):
+        Frame::getAngularVelocityInGround.  A frame welded to a body has the
+        body's angular velocity; ground's is 0.  For angular-velocity
+        references computed from states, and for synthesizing data; not on
+        the hot path."""
+        fr = self.find_frame(path)
+        if fr is None:
+            raise ValueError(f"no frame '{path}' in the model")
+        return self._body_angular_velocities_in_ground(coordinates, speeds)[fr[0]]
+
+    def _body_angular_velocities_in_ground(self, coordinates: Dict[str, float],
+                                           speeds: Dict[str, float]) -> Dict[str, np.ndarray]:
+        """Every body's angular velocity in ground: along the tree, the
+        parent's plus, for each rotation axis of the joint that a coordinate
+        moves, (the axis in ground, after the joint's earlier rotations) x
+        (the axis function's slope) x (the coordinate's speed)."""
+        from .splines import SimmSpline
+        X_G = self._body_transforms_in_ground(coordinates)
+        qdefault = {c.name: c.default_value for c in self.coordinates()}
+        w_G = {"ground": np.zeros(3)}
+        for j in self.tree_order():
+            R_GF = X_G[j.parent][:3, :3] @ body_fixed_xyz(j.orient_in_parent)
+            R_cur, w = np.eye(3), w_G[j.parent].copy()
+            for ax in j.axes:
+                if ax.type != abi.MH_AXIS_ROTATION:
+                    continue
+                f, a = ax.func, np.asarray(unit3(ax.dir))
+                if f.kind == abi.MH_FN_CONSTANT:
+                    t = f.a
+                else:
+                    q = float(coordinates.get(f.coord, qdefault.get(f.coord, 0.0)))
+                    if f.kind == abi.MH_FN_LINEAR:
+                        t, slope = f.scale * (f.a * q + f.b), f.scale * f.a
+                    else:
+                        sp = SimmSpline(f.x, f.y)
+                        t, slope = f.scale * float(sp(q)), f.scale * float(sp(q, deriv=1))
+                    w = w + (R_GF @ R_cur @ a) * (slope * float(speeds.get(f.coord, 0.0)))
+                K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+                R_cur = R_cur @ (np.eye(3) + math.sin(t) * K + (1.0 - math.cos(t)) * (K @ K))
+            w_G[j.child] = w
+        return w_G
+
     def marker_locations_in_ground(self, coordinates: Dict[str, float]) -> Dict[str, np.ndarray]:
         """Every marker's location in ground (by marker path) at the given
         coordinate values (by coordinate name; a missing one is at its

@@ -280,10 +280,15 @@ class _FrameTrackingGoal:
                                  f"{label} does not correspond to any model state.")
         bypath = {c.path + "/value": c.name for c in model.coordinates()}
         cols = {bypath[k]: np.asarray(v, float) for k, v in ref.columns.items() if k in bypath}
-        pick = 0 if self.WHAT == "translation" else 1
-        vals = [[model.frame_pose_in_ground(p, {n: v[r] for n, v in cols.items()})[pick] for p in paths]
-                for r in range(len(ref.times))]
+        vals = self._values_from_states(model, paths, ref, cols)
         return np.asarray(ref.times, float), np.asarray(vals, float)
+
+    def _values_from_states(self, model: Model, paths: List[str], ref: DataTable, cols):
+        """values[row][frame] at the states table's rows; cols: the coordinate
+        values by coordinate name."""
+        pick = 0 if self.WHAT == "translation" else 1
+        return [[model.frame_pose_in_ground(p, {n: v[r] for n, v in cols.items()})[pick] for p in paths]
+                for r in range(len(ref.times))]
 
     def reference_table(self, model: Model) -> DataTable:
         """The flattened reference: <frame path>/position_x|y|z or
@@ -332,6 +337,58 @@ class MocoOrientationTrackingGoal(_FrameTrackingGoal):
     @staticmethod
     def _flatten(v):
         return np.stack([rotation_to_quaternion(R) for R in np.asarray(v, float).reshape(len(v), 3, 3)])
+
+
+@dataclass
+class MocoAngularVelocityTrackingGoal(_FrameTrackingGoal):
+    """MocoAngularVelocityTrackingGoal (Moco/Moco/MocoGoal/
+    MocoAngularVelocityTrackingGoal.{h,cpp}): the integral over the phase of
+    sum_f w_f |angular velocity of model frame f in ground - reference_f(t)|^2,
+    times the weight (include/mocohip.h MH_GOAL_ANGULAR_VELOCITY_TRACKING).
+    ``reference`` holds Vec3 columns (``values[row][frame][xyz]``, expressed in
+    ground); with ``states_reference`` the angular velocities are computed at
+    every row from the row's coordinate values and speeds (realizeVelocity),
+    and the table needs the speed column of every coordinate that turns a
+    tracked frame."""
+    name: str = "angular_velocity_tracking"
+    WHAT = "angular velocity"
+    SUFFIXES = ("angular_velocity_x", "angular_velocity_y", "angular_velocity_z")
+
+    @staticmethod
+    def _flatten(v):
+        return np.asarray(v, float).reshape(len(v), 3)
+
+    @staticmethod
+    def turning_coordinates(model: Model, paths: List[str]) -> List[str]:
+        """The coordinates (by name, model order) that are the argument of a
+        non-constant function on a rotation axis of a joint between ground
+        and one of the frames: the speeds the frames' angular velocities
+        depend on."""
+        parent_joint = {j.child: j for j in model.joints}
+        names = set()
+        for path in paths:
+            body = model.find_frame(path)[0]
+            while body != "ground":
+                j = parent_joint[body]
+                names.update(ax.func.coord for ax in j.axes
+                             if ax.type == abi.MH_AXIS_ROTATION and ax.func.kind != abi.MH_FN_CONSTANT)
+                body = j.parent
+        return [c.name for c in model.coordinates() if c.name in names]
+
+    def _values_from_states(self, model: Model, paths: List[str], ref: DataTable, cols):
+        bypath = {c.name: c.path + "/speed" for c in model.coordinates()}
+        speeds = {}
+        for name in self.turning_coordinates(model, paths):
+            if bypath[name] not in ref.columns:
+                raise ValueError(f"{type(self).__name__}: the states reference has no column '{bypath[name]}', "
+                                 "which the angular velocity of a tracked frame depends on")
+            speeds[name] = np.asarray(ref.columns[bypath[name]], float)
+        vals = []
+        for r in range(len(ref.times)):
+            w = model._body_angular_velocities_in_ground({n: v[r] for n, v in cols.items()},
+                                                         {n: v[r] for n, v in speeds.items()})
+            vals.append([w[model.find_frame(p)[0]] for p in paths])
+        return vals
 
 
 # ------------------------------------------------- functions of time ----
@@ -673,7 +730,8 @@ class ProblemRep:
                                               "(the coordinates are not NLP states)")
                 gs.kind = abi.MH_GOAL_MARKER_TRACKING
                 self._marker_tracking_terms(model, g, gs, gidx, gcol, gw)
-            elif isinstance(g, (MocoTranslationTrackingGoal, MocoOrientationTrackingGoal)):
+            elif isinstance(g, (MocoTranslationTrackingGoal, MocoOrientationTrackingGoal,
+                                MocoAngularVelocityTrackingGoal)):
                 if kin is not None:
                     raise NotImplementedError(f"{type(g).__name__} with prescribed kinematics "
                                               "(the coordinates are not NLP states)")
@@ -964,10 +1022,14 @@ class ProblemRep:
     def _frame_tracking_terms(self, model: Model, g: "_FrameTrackingGoal", gs, gidx, gcol, gw):
         """MocoTranslationTrackingGoal / MocoOrientationTrackingGoal::
         initializeOnModelImpl: four terms per tracked frame (kind 9, as a
-        marker's) or ten (kind 10: R_BO, the quaternion columns, the weight);
+        marker's; kind 12: the angular-velocity columns with zero weights,
+        then the weight) or ten (kind 10: R_BO, the quaternion columns, the
+        weight);
         include/mocohip.h."""
         orient = isinstance(g, MocoOrientationTrackingGoal)
-        gs.kind = abi.MH_GOAL_ORIENTATION_TRACKING if orient else abi.MH_GOAL_TRANSLATION_TRACKING
+        angvel = isinstance(g, MocoAngularVelocityTrackingGoal)
+        gs.kind = (abi.MH_GOAL_ORIENTATION_TRACKING if orient else
+                   abi.MH_GOAL_ANGULAR_VELOCITY_TRACKING if angvel else abi.MH_GOAL_TRANSLATION_TRACKING)
         paths = g.tracked_frame_paths()
         name = g.reference_name()
         if name not in self.compiled.table_index:
@@ -993,8 +1055,8 @@ class ProblemRep:
                 for k in range(9):
                     gidx.append(body); gcol.append(ci[k] if k < 4 else -1); gw.append(float(R[k // 3, k % 3]))
             else:
-                for c in range(3):
-                    gidx.append(body); gcol.append(ci[c]); gw.append(float(fr[1][c]))
+                for c in range(3):   # angular velocity: the frame's location is not used
+                    gidx.append(body); gcol.append(ci[c]); gw.append(0.0 if angvel else float(fr[1][c]))
             gidx.append(body); gcol.append(-1); gw.append(w)
 
     @staticmethod
