@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void k_kkt_gemm(const KTask* __restrict__ task
         }
     };
     double pv[PL], qv[QL];
-    load(0, pv, qv);
+    if (nsteps > 0) load(0, pv, qv);                       // K = 0 (no shared columns): no tile, C = beta C
     for (int step = 0; step < nsteps; ++step) {
 #pragma unroll
         for (int u = 0; u < PL; ++u) Ps[pkk[u]][pii[u]] = pv[u];

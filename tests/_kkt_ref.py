@@ -31,13 +31,29 @@ def schur_blocks(bm, A, w, dc):
     return D, E
 
 
-def cr_factor(D, E):
+def _tri_inv(L):
+    """inv(L) of a lower-triangular L, formed explicitly."""
+    from scipy.linalg import solve_triangular
+    return np.tril(solve_triangular(L, np.eye(len(L)), lower=True))
+
+
+def cr_factor(D, E, inverse=False):
     """Block cyclic reduction of the SPD block-tridiagonal matrix with
     diagonal blocks D and sub-diagonal blocks E (E[b] = S[b+1, b]).  Returns
     the per-block factors (L, U, V) and the level schedule: at level l the
     active blocks are every 2^l-th, the odd ones among them are eliminated:
     L_i L_i^T = D_i, U_i = L_i^-1 S[i, left], V_i = L_i^-1 S[i, right]; the
-    even ones are updated D_j -= U^T U + V^T V and coupled by -V^T U."""
+    even ones are updated D_j -= U^T U + V^T V and coupled by -V^T U.
+    inverse=True restates the device's default path (r <= 160): L[i] holds
+    inv(L_i), formed explicitly, and U, V are products with it -- the same
+    algorithm with that path's own rounding (~cond(L_i) eps per product)."""
+    def chol(a):
+        c = np.linalg.cholesky(a)
+        return _tri_inv(c) if inverse else c
+
+    def lsolve(l, b):
+        return l @ b if inverse else np.linalg.solve(l, b)
+
     D = D.copy()
     E = E.copy()
     nb = len(D)
@@ -49,7 +65,7 @@ def cr_factor(D, E):
     while True:
         if len(active) == 1:
             i = active[0]
-            L[i] = np.linalg.cholesky(D[i])
+            L[i] = chol(D[i])
             levels.append(([i], {i: (None, None)}))
             break
         odd = active[1::2]
@@ -59,10 +75,10 @@ def cr_factor(D, E):
             left = active[k - 1]
             right = active[k + 1] if k + 1 < len(active) else None
             nbr[i] = (left, right)
-            L[i] = np.linalg.cholesky(D[i])
-            U[i] = np.linalg.solve(L[i], E[left])             # S[i, left] = E[left]
+            L[i] = chol(D[i])
+            U[i] = lsolve(L[i], E[left])                      # S[i, left] = E[left]
             if right is not None:
-                V[i] = np.linalg.solve(L[i], E[i].T)          # S[i, right] = E[i]^T
+                V[i] = lsolve(L[i], E[i].T)                   # S[i, right] = E[i]^T
         for k in range(0, len(active), 2):
             j = active[k]
             if k - 1 >= 0:
@@ -78,12 +94,13 @@ def cr_factor(D, E):
     return L, U, V, levels
 
 
-def cr_solve(L, U, V, levels, B):
-    """S^-1 B, B [nb, r, k]."""
+def cr_solve(L, U, V, levels, B, inverse=False):
+    """S^-1 B, B [nb, r, k]; inverse=True with the factors of
+    cr_factor(inverse=True): every triangular solve a product with inv(L_i)."""
     X = B.copy()
     for odd, nbr in levels:                                  # forward
         for i in odd:
-            X[i] = np.linalg.solve(L[i], X[i])
+            X[i] = L[i] @ X[i] if inverse else np.linalg.solve(L[i], X[i])
             left, right = nbr[i]
             if left is not None:
                 X[left] -= U[i].T @ X[i]
@@ -97,7 +114,7 @@ def cr_solve(L, U, V, levels, B):
                 y -= U[i] @ X[left]
             if right is not None:
                 y -= V[i] @ X[right]
-            X[i] = np.linalg.solve(L[i].T, y)
+            X[i] = L[i].T @ y if inverse else np.linalg.solve(L[i].T, y)
     return X
 
 

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 import _kkt_ref as K
+import _kkt_synth as SY
 from mocohip import configs
 from mocohip.kkt import block_map
 from mocohip.solver import OracleNLP
@@ -97,3 +98,85 @@ def test_block_cyclic_reduction_solves_the_schur_complement(name):
     X = K.from_blocks(bm, K.cr_solve(Lf, U, V, levels, K.to_blocks(bm, B)))
     Xd = np.linalg.solve(S, B)
     assert np.abs(X - Xd).max() <= 1e-8 * np.abs(Xd).max()
+
+
+# ------------------------------------------------------------------------
+# the synthetic layouts of tests/_kkt_synth.py (what tests/test_kkt_kernels_gpu.py
+# runs on the device): the generator and both restatements, without a GPU
+# ------------------------------------------------------------------------
+@pytest.mark.parametrize("name", sorted({lay.host for lay in SY.LAYOUTS.values()}))
+def test_synth_host_shapes(name):
+    """The (n, m, nnz) the layouts are generated for are the contexts'."""
+    make, shape = SY.host(name)
+    st = make()
+    nlp = OracleNLP(st.problem.create_rep(), st.solver.options())
+    assert (nlp.n, nlp.m, nlp.nnz) == shape
+
+
+def test_synth_block_map_refuses_bad_shapes():
+    rng = np.random.default_rng(0)
+    with pytest.raises(ValueError, match="three blocks"):
+        SY.synth_block_map(740, 558, 3969, 4, 144, 100, 64, 2, rng)     # 2 P > c
+    with pytest.raises(ValueError, match="columns"):
+        SY.synth_block_map(29, 20, 148, 4, 5, 12, 4, 1, rng)            # chain longer than n
+    with pytest.raises(ValueError, match="rows"):
+        SY.synth_block_map(389, 320, 2368, 16, 19, 12, 4, 1, rng)
+    with pytest.raises(ValueError, match="slots"):
+        SY.synth_block_map(464, 312, 28812, 3, 104, 60, 20, 2, rng)
+
+
+@pytest.mark.parametrize("name", sorted(SY.LAYOUTS))
+def test_synth_layout(name):
+    """A synthetic layout places every nonzero once, leaves a row, a column
+    and the columns past the chain empty, gives a block-tridiagonal S with
+    the blocks of schur_blocks and cond(S) <= 1e3 (a condition on the input,
+    not a measurement: a layout that breaks it gets another c, P or nd), and
+    both restatements -- substitution and explicit inverses -- solve it to
+    1e-13 of a dense solve refined in long double."""
+    lay = SY.LAYOUTS[name]
+    bm, vals, rs, w, dc = SY.problem(name)
+    assert (bm.nb, bm.r, bm.c, bm.nshare, bm.nd) == (lay.nb, lay.r, lay.c, lay.P, lay.nd)
+    src = np.concatenate([bm.a_src[bm.a_src >= 0], bm.d_src[bm.d_src >= 0]])
+    assert np.array_equal(np.sort(src), np.arange(bm.nnz))              # every nonzero exactly once
+    assert not np.array_equal(src, np.arange(bm.nnz))                   # and not in slot order
+    rows = np.sort(bm.rowmap[bm.rowmap >= 0])
+    assert np.array_equal(rows, np.arange(bm.m))                        # every row in exactly one block
+    assert (bm.rowmap >= 0).sum(axis=1).max() <= bm.r
+    P = bm.nshare
+    for b in range(bm.nb - 1):
+        assert np.array_equal(bm.colmap[b, bm.rshare[b]:bm.rshare[b] + P],
+                              bm.colmap[b + 1, bm.lshare[b + 1]:bm.lshare[b + 1] + P])
+        assert not set(bm.colmap[b, :bm.rshare[b]]) & set(bm.colmap[b + 1])
+    for j in np.unique(bm.colmap):                                      # col2: the column's A positions
+        pos = np.flatnonzero(bm.colmap.ravel() == j)
+        assert sorted(p for p in bm.col2[j] if p >= 0) == pos.tolist()
+    assert (bm.col2[bm.dcols] == -1).all()
+    S, J = K.dense_schur(bm, vals, rs, w, dc)
+    used_rows, used_cols = np.abs(J).sum(axis=1) > 0, np.abs(J).sum(axis=0) > 0
+    if bm.nd:
+        used_rows |= (bm.d_src >= 0).any(axis=1)
+    assert not used_rows.all() and not used_cols[bm.nd:bm.colmap.max() + 1].all()
+    assert bm.colmap.max() + 1 < bm.n                                   # columns beyond the chain
+    A, _ = K.gather(bm, vals, rs)
+    D, E = K.schur_blocks(bm, A, w, dc)
+    blk = -np.ones(bm.m, int)
+    loc = -np.ones(bm.m, int)
+    for b in range(bm.nb):
+        ok = bm.rowmap[b] >= 0
+        blk[bm.rowmap[b, ok]] = b
+        loc[bm.rowmap[b, ok]] = np.where(ok)[0]
+    assert not S[np.abs(blk[:, None] - blk[None, :]) > 1].any()
+    for b in range(bm.nb):
+        rr = bm.rowmap[b][bm.rowmap[b] >= 0]
+        np.testing.assert_allclose(D[b][np.ix_(loc[rr], loc[rr])], S[np.ix_(rr, rr)], rtol=0, atol=1e-13)
+        if b + 1 < bm.nb:
+            r2 = bm.rowmap[b + 1][bm.rowmap[b + 1] >= 0]
+            np.testing.assert_allclose(E[b][np.ix_(loc[r2], loc[rr])], S[np.ix_(r2, rr)], rtol=0, atol=1e-13)
+            assert E[b].any() == (P > 0)
+    ref = SY.reference(name)
+    print(f"{name}: cond(S) = {ref.cond:.1f}")
+    assert ref.cond <= 1e3
+    for path in ("substitution", "inverse"):
+        e = SY.rel_err(ref.X[path], ref.Xd)
+        print(f"{name}: {path} restatement vs refined dense solve {e:.1e}")
+        assert e <= 1e-13

@@ -104,7 +104,10 @@ def test_device_kkt_matches_restatement(name, path, monkeypatch):
         nlp.close()
 
 
-def test_device_kkt_reports_indefinite():
+@pytest.mark.parametrize("path", ["inverse", "substitution"])
+def test_device_kkt_reports_indefinite(path, monkeypatch):
+    """Both paths' failure flag: k_kkt_potri's and k_kkt_potrf's."""
+    monkeypatch.setenv("MOCOHIP_KKT_INV", "1" if path == "inverse" else "0")
     nlp, x, rng = _setup("gait_rigid")
     try:
         dk = nlp.device_kkt()
