@@ -443,7 +443,73 @@ enum mh_goal_kind {
      * The goals of this kind share the launch of kinds 7, 9 and 10: a body that
      * carries an orientation and an angular-velocity item is walked once per
      * lane. */
-    MH_GOAL_ANGULAR_VELOCITY_TRACKING = 12
+    MH_GOAL_ANGULAR_VELOCITY_TRACKING = 12,
+    /* (13 is not assigned either: a goal of kind 13 is refused as unknown.) */
+    /* MocoJointReactionGoal (MocoJointReactionGoal.{h,cpp}): weight * duration
+     * * quadrature over every grid point of
+     *     L = (sum over the six measures i of w_i r_i^2) / denominator
+     * r = the reaction load of one joint: the moment (x, y, z) and the force
+     * (x, y, z) that the joint applies to its child (or parent) body, taken
+     * at that joint frame's origin and expressed in a chosen frame.
+     * One goal tracks one joint, named by its child body b (an mh_model body
+     * index; every body has exactly one inboard joint).  Sixteen consecutive
+     * terms, goal_index = b in all of them:
+     *   terms 0-8:  goal_weight = R_EO row-major, the orientation of the
+     *               expressed-in frame in its body; goal_column = that body e
+     *               (-1 = ground), the same in all nine;
+     *   terms 9-14: goal_weight = the weights of moment-x, -y, -z, force-x,
+     *               -y, -z, each >= 0 (0: measure not selected);
+     *               goal_column = -1;
+     *   term 15:    goal_column = the loads frame (0 = parent, 1 = child);
+     *               goal_weight = the denominator (> 0, finite): total body
+     *               mass x |gravity| when |gravity| > eps^0.875
+     *               (SimTK::SignificantReal), else the total mass
+     *               (MocoJointReactionGoal.cpp:44-48, .h:110).
+     * mh_goal.table and mh_goal.exponent are unused.
+     * Accelerations: with implicit multibody dynamics the iterate's
+     * acceleration variables; with explicit dynamics the udot that the DAE
+     * solves at the point (M udot = f).  Not with prescribed kinematics and
+     * not with MocoParameters (MH_ERR_UNSUPPORTED: the load reads the mass
+     * properties, and the goals' gradient along a parameter is defined as 0).
+     * Kinematic constraints (couplers) are accepted: their forces are mobility
+     * forces, which reach the load only through udot.
+     * Per grid point, each operation rounded on its own (no fused
+     * multiply-add), every sum of three products formed as
+     * (a0 b0 + a1 b1) + a2 b2:
+     *   1. F = the spatial force that b's inboard joint transmits to b, in
+     *      ground, about the ground origin: the sum over b's subtree of
+     *      (I a + v x* I v - applied body forces) of the recursive
+     *      Newton-Euler pass with the point's accelerations, gravity as the
+     *      fictitious base acceleration, the muscles' point forces and the
+     *      external loads among the applied forces (the generic interpreter's
+     *      body-force array after its backward pass).  n = its moment part,
+     *      f = its force part.
+     *   2. on the child:  o = p_Gb + R_Gb p_BM (the child joint frame's
+     *                     origin); c = o x f = (o1 f2 - o2 f1, o2 f0 - o0 f2,
+     *                     o0 f1 - o1 f0); moment = n - c; force = f
+     *      on the parent: o = p_Gp + R_Gp p_PF (the parent joint frame's
+     *                     origin, p = b's parent, ground: o = p_PF);
+     *                     moment = -(n - c); force = -f
+     *      (OpenSim shifts the child's reaction to the parent frame's origin
+     *      and negates it.)
+     *   3. R_GE = R_Ge R_EO (ground: R_GE = R_EO);
+     *      r = (R_GE^T moment, R_GE^T force)
+     *   4. L = 0.0; for i = 0..5: L = L + w_i * (r_i * r_i); L = L / denominator
+     * Not pinned: the reaction is defined here as the total inter-body load --
+     * the component along the joint's own mobility (a CoordinateActuator's
+     * torque about a pin axis, for example) is part of it.  This is taken to be
+     * what Simbody's calcMobilizerReactionForces returns; no Simbody was
+     * available to confirm it.  The reference divides the integral by the
+     * denominator once and sums only the selected measures in the user's
+     * order: ulp-level reassociations of the above, not pinned either.
+     * Gradient: finite-difference quotients of the whole integrand with
+     * k_grad's formulas over t0, tf and every point input but the slacks
+     * (states, controls, accelerations / auxiliary derivatives, multipliers),
+     * one DAE evaluation (explicit dynamics: two) per direction and grid
+     * point, added to the entries the other goals wrote.  Goals of this kind
+     * on one problem share the evaluations.  mh_batch_* accepts contexts with
+     * such goals and never reads them, as for every other goal. */
+    MH_GOAL_JOINT_REACTION = 14
 };
 typedef struct mh_goal {
     int32_t kind;
@@ -872,6 +938,13 @@ int mh_batch_set_group_results_global(mh_batch* batch, int global_memory);
  * parity tests. */
 int mh_eval_dae(mh_ctx* ctx, int32_t npoints, const double* inputs,
         double* outputs);
+/* The reaction load of goal `goal` (of kind MH_GOAL_JOINT_REACTION; any
+ * other goal: MH_ERR_INVALID) at npoints rows [time, NI point inputs], as for
+ * mh_eval_dae: out holds 6 doubles per row, the moment x, y, z and then the
+ * force x, y, z, on the goal's loads frame and expressed in its expressed-in
+ * frame (r of MH_GOAL_JOINT_REACTION, step 3).  Synchronous. */
+int mh_eval_joint_reaction(mh_ctx* ctx, int32_t goal, int32_t npoints, const double* inputs,
+        double* out);
 /* Path-constraint probe, the counterpart of mh_eval_dae for the path
  * callback: the npath path-equation values of npoints probe rows [time, point
  * inputs (NS + NC + NDV + ...)] (the row of mh_get_callback_sparsity, W

@@ -33,6 +33,7 @@
 #include <OpenSim/Moco/MocoGoal/MocoMarkerFinalGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoMarkerTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoAngularVelocityTrackingGoal.h>
+#include <OpenSim/Moco/MocoGoal/MocoJointReactionGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoOrientationTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoTranslationTrackingGoal.h>
 #include <OpenSim/Simulation/StatesTrajectory.h>
@@ -635,6 +636,39 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
             for (const auto& path : paths) {
                 hg.weights.push_back({path, ws.contains(path) ? ws.get(path).getWeight() : 1.0});
                 if (!model.hasComponent<Frame>(path)) continue;   // make_rep: no frame
+                const Frame& f = model.getComponent<Frame>(path);
+                const Frame& base = f.findBaseFrame();
+                const SimTK::Transform X_BO = f.findTransformInBaseFrame();
+                const SimTK::Vec3 xyz = X_BO.R().convertRotationToBodyFixedXYZ();
+                mhb::OffsetFrame of;
+                of.name = path;
+                of.path = path;
+                of.body = &base == &model.getGround() ? "ground" : base.getName();
+                for (int d = 0; d < 3; ++d) {
+                    of.translation[d] = X_BO.p()[d];
+                    of.orientation[d] = xyz[d];
+                }
+                prob.model.add_offset_frame(of);
+            }
+        } else if (dynamic_cast<const MocoJointReactionGoal*>(&g)) {
+            // the properties as they are (the goal has setters only: read by
+            // name); the joint by its name (mhb::make_rep
+            // resolves /jointset/<name> or the name) and the expressed-in
+            // frame as an offset frame of its base frame with its orientation.
+            // mhb::make_rep runs initializeOnModelImpl's checks and computes
+            // the denominator (total mass x |gravity|) from the lowered model.
+            hg.kind = mhb::Goal::JOINT_REACTION;
+            hg.joint_path = g.getPropertyByName("joint_path").getValue<std::string>();
+            if (!hg.joint_path.empty() && model.hasComponent<Joint>(hg.joint_path))
+                hg.joint_path = model.getComponent<Joint>(hg.joint_path).getName();
+            hg.loads_frame = g.getPropertyByName("loads_frame").getValue<std::string>();
+            hg.expressed_in_frame_path = g.getPropertyByName("expressed_in_frame_path").getValue<std::string>();
+            const auto& measures = g.getPropertyByName("reaction_measures");
+            for (int i = 0; i < measures.size(); ++i) hg.reaction_measures.push_back(measures.getValue<std::string>(i));
+            const auto& ws = g.getPropertyByName("reaction_weights").getValue<MocoWeightSet>();
+            for (int i = 0; i < ws.getSize(); ++i) hg.weights.push_back({ws.get(i).getName(), ws.get(i).getWeight()});
+            const std::string& path = hg.expressed_in_frame_path;
+            if (!path.empty() && model.hasComponent<Frame>(path)) {   // (else make_rep: no frame)
                 const Frame& f = model.getComponent<Frame>(path);
                 const Frame& base = f.findBaseFrame();
                 const SimTK::Transform X_BO = f.findTransformInBaseFrame();

@@ -2205,7 +2205,10 @@ __host__ __device__ __forceinline__ bool goal_tracked_items(int kind) {
 }
 // Goals with an integral (quadrature of an integrand): all but the endpoint
 // costs (final time, final marker) and the marker / frame tracking goals, whose
-// integrand and gradient k_marker_tracking writes into the same slots.
+// integrand and gradient k_marker_tracking writes into the same slots.  The
+// joint-reaction goal (kind 14) is an integral goal: goal_integrand gives 0.0
+// for it, and k_joint_reaction / k_joint_reaction_grad write its slot and add
+// its gradient after k_integrand / k_grad.
 __host__ __device__ __forceinline__ bool goal_integral(int kind) {
     return kind != MH_GOAL_FINAL_TIME && kind != MH_GOAL_MARKER_FINAL && !goal_tracked_items(kind);
 }
@@ -2377,7 +2380,6 @@ __global__ void __launch_bounds__(64) k_grad(DevModel M, Layout L, GoalSet GS, i
     else if (d - 2 < L.NS + L.NC + L.NDV) grad[L.DB + (long)k * L.NDV + (d - 2 - L.NS - L.NC)] = acc;
     else grad[L.XM + (long)k * L.NM + (d - 2 - L.NS - L.NC - L.NDV)] = acc;
 }
-
 
 // DAE probe: one lane per input row [time, states, controls].
 template <class D>
@@ -2583,6 +2585,12 @@ struct mh_ctx {
     MarkerTrack MT{};
     std::vector<int> mt_tab;
     size_t mt_lds[2] = {0, 0};
+    // joint-reaction goals (kind 14): their count, the lanes of
+    // k_joint_reaction in gradient mode (ND = NI - NSL + 2) and its lane
+    // values [G][stride][njr]
+    int njr = 0;
+    Lanes lanes_jr{};
+    double* d_jr = nullptr;
     bool use_roles = false;        // MOCOHIP_ROLES=1: k_role (+ k_couple) for the Jacobian lanes
     int role_threads = 256;        // k_role workgroup size (MOCOHIP_ROLE_THREADS: 64..512)
     int iv_threads = 1024;         // k_interval workgroup size, Jacobian lanes (MOCOHIP_IV_THREADS: 256..1024)
@@ -3047,6 +3055,18 @@ static constexpr Backend make_backend_tasks(const char* name, double flops) {
 
 // Generic device-interpreter back ends (generic.hip), one per size class.
 const Backend* generic_backends();
+// The joint-reaction goals' kernels (joint_reaction.hip), by size class as
+// generic_backends(): they run the generic interpreter whatever back end
+// serves g and J (a generated back end has no body-level forces to read).
+// eval: the goals' integrands (mode 0) or integrands and gradient parts (mode
+// 1); probe: mh_eval_joint_reaction's rows.  A translation unit of their own,
+// so that generic.hip compiles to the code it had without them (the inlining
+// of dae_eval into k_eval_lds depends on the unit's other call sites).
+struct JointReactionBackend {
+    void (*eval)(mh_ctx*, const double* x, int mode);
+    void (*probe)(mh_ctx*, int goal, int np, const double* in, double* out);
+};
+const JointReactionBackend* joint_reaction_backends();
 // A model-specialized back end (generated/gen_<model>.hip): the task kernels
 // (default) and the one-lane-per-DAE kernel (MOCOHIP_BACKEND=lane), for the
 // model structure match() accepts (multibody dynamics mode and prescribed

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <sstream>
 #include <stdexcept>
 
@@ -926,6 +927,67 @@ void make_rep(const Problem& P, ProblemRep& R) {
             }
             break;
         }
+        case Goal::JOINT_REACTION: {
+            // MocoJointReactionGoal::initializeOnModelImpl (problem.py
+            // _joint_reaction_terms): sixteen terms -- R_EO with the
+            // expressed-in body, the six measure weights, the loads frame
+            // with the denominator
+            if (presc) fail("MocoJointReactionGoal with prescribed kinematics (the accelerations are not the NLP's)");
+            if (!P.parameters.empty())
+                fail("MocoJointReactionGoal with MocoParameters (the load reads the mass properties)");
+            gs.kind = MH_GOAL_JOINT_REACTION;
+            static const char* const measures[6] = {"moment-x", "moment-y", "moment-z", "force-x", "force-y",
+                                                    "force-z"};
+            if (g.joint_path.empty()) fail("Expected a joint path, but property joint_path is empty.");
+            if (g.loads_frame != "parent" && g.loads_frame != "child")
+                fail("Property 'loads_frame' (in object '" + g.name + "' of type MocoJointReactionGoal) has "
+                     "invalid value " + g.loads_frame + "; expected one of the following:  child  parent.");
+            double w6[6] = {0, 0, 0, 0, 0, 0};
+            bool chosen[6] = {false, false, false, false, false, false};
+            for (auto& m : g.reaction_measures) {
+                int i = 0;
+                while (i < 6 && m != measures[i]) ++i;
+                if (i == 6) fail("Reaction measure '" + m + "' not recognized.");
+                chosen[i] = true;
+            }
+            for (int i = 0; i < 6; ++i)
+                if (g.reaction_measures.empty() || chosen[i]) {
+                    w6[i] = 1.0;
+                    for (auto& kv : g.weights)
+                        if (kv.first == measures[i]) w6[i] = kv.second;
+                }
+            const Joint* joint = nullptr;
+            for (auto& j : model.joints)
+                if (!joint && (g.joint_path == j.name || g.joint_path == "/jointset/" + j.name)) joint = &j;
+            if (!joint) fail("MocoJointReactionGoal: no joint '" + g.joint_path + "' in the model");
+            for (int i = 0; i < 6; ++i)
+                if (w6[i] < 0)
+                    fail("MocoJointReactionGoal: negative weight " + num(w6[i]) + " of measure '" + measures[i] + "'");
+            const bool child = g.loads_frame == "child";
+            const int b = R.cm.index_of_body(joint->child);
+            int e;
+            double R_EO[9];
+            if (!g.expressed_in_frame_path.empty()) {
+                std::string body_name;
+                double loc[3];
+                if (!model.find_frame(g.expressed_in_frame_path, body_name, loc, R_EO))
+                    fail("MocoJointReactionGoal: no frame '" + g.expressed_in_frame_path + "' in the model");
+                e = R.cm.index_of_body(body_name);
+            } else {   // the joint's own frame on that side
+                e = R.cm.index_of_body(child ? joint->child : joint->parent);
+                body_fixed_xyz(child ? joint->orient_in_child : joint->orient_in_parent, R_EO);
+            }
+            // Model::getTotalMass x |gravity| (the total mass without gravity)
+            double den = 0.0;
+            for (auto& body : model.bodies) den += body.mass;
+            const double* gv = model.gravity;
+            const double gmag = std::sqrt((gv[0] * gv[0] + gv[1] * gv[1]) + gv[2] * gv[2]);
+            if (gmag > std::pow(std::numeric_limits<double>::epsilon(), 0.875)) den *= gmag;   // SimTK::SignificantReal
+            for (int k = 0; k < 9; ++k) term(b, e, R_EO[k]);
+            for (int i = 0; i < 6; ++i) term(b, -1, w6[i]);
+            term(b, child ? 1 : 0, den);
+            break;
+        }
         case Goal::AUX_DERIVATIVES: {
             gs.kind = MH_GOAL_AUX_DERIVATIVES;
             int naux = 0;
@@ -1446,6 +1508,13 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
                        : (kind == "orientation_tracking" ? Goal::ORIENTATION_TRACKING
                                                          : Goal::ANGULAR_VELOCITY_TRACKING);
                 g.name = t.s(); g.weight = t.d(); g.table = t.s();
+                g.weights = read_weights(t);
+            } else if (kind == "joint_reaction") {
+                g.kind = Goal::JOINT_REACTION;
+                g.name = t.s(); g.weight = t.d(); g.joint_path = t.s(); g.loads_frame = t.s();
+                g.expressed_in_frame_path = t.s();
+                const long nm = t.i();
+                for (long k = 0; k < nm; ++k) g.reaction_measures.push_back(t.s());
                 g.weights = read_weights(t);
             } else if (kind == "aux_derivatives") {
                 g.kind = Goal::AUX_DERIVATIVES;

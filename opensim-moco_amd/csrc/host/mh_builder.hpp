@@ -248,7 +248,7 @@ struct VariableInfo {
 struct Goal {
     enum Kind { CONTROL, STATE_TRACKING, FINAL_TIME, SUM_SQUARED_STATE, INITIAL_ACTIVATION, MARKER_FINAL,
                 AUX_DERIVATIVES, MARKER_TRACKING, TRANSLATION_TRACKING, ORIENTATION_TRACKING,
-                ANGULAR_VELOCITY_TRACKING };
+                ANGULAR_VELOCITY_TRACKING, JOINT_REACTION };
     Kind kind = CONTROL;
     std::string name;
     double weight = 1.0;
@@ -267,6 +267,10 @@ struct Goal {
     std::string mode = "endpoint_constraint";               // initial activation
     std::string point_name;                                 // marker final
     double reference_location[3] = {0, 0, 0};
+    // joint reaction (problem.py MocoJointReactionGoal): the measures' weights
+    // (reaction_weights) are in `weights`
+    std::string joint_path, loads_frame = "parent", expressed_in_frame_path;
+    std::vector<std::string> reaction_measures;
 };
 
 // Bound function of MocoControlBoundConstraint: OpenSim::Constant,

@@ -1929,6 +1929,43 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
         const int tn = G.kind == MH_GOAL_ORIENTATION_TRACKING ? 10 : 4;
         const int tcols = G.kind == MH_GOAL_ORIENTATION_TRACKING ? 4 : 3;   // leading terms with a column
         const bool marker = G.kind == MH_GOAL_MARKER_FINAL || tracking;
+        if (G.kind == MH_GOAL_JOINT_REACTION) {
+            // sixteen terms (include/mocohip.h): R_EO with the expressed-in
+            // body, the six measure weights, the loads frame and denominator
+            if (G.term_begin < 0 || G.term_count != 16 || (int64_t)G.term_begin + G.term_count > p->nterms)
+                return set_err(MH_ERR_INVALID, "goal %d: joint reaction goal needs 16 terms", g);
+            if (c->presc)
+                return set_err(MH_ERR_UNSUPPORTED, "goal %d: joint reaction goal with prescribed kinematics", g);
+            if (p->nparameters > 0)
+                return set_err(MH_ERR_UNSUPPORTED, "goal %d: joint reaction goal with MocoParameters", g);
+            const int tb = G.term_begin, b = p->goal_index[tb];
+            if (b < 0 || b >= M.nbodies)
+                return set_err(MH_ERR_INVALID, "goal %d: joint reaction goal: child body %d out of range", g, b);
+            for (int k = 1; k < 16; ++k)
+                if (p->goal_index[tb + k] != b)
+                    return set_err(MH_ERR_INVALID, "goal %d: term %d: a joint reaction goal's terms name different "
+                                   "bodies", g, tb + k);
+            const int e = p->goal_column[tb];
+            if (e < -1 || e >= M.nbodies)
+                return set_err(MH_ERR_INVALID, "goal %d: joint reaction goal: expressed-in body %d out of range", g,
+                               e);
+            for (int k = 1; k < 9; ++k)
+                if (p->goal_column[tb + k] != e)
+                    return set_err(MH_ERR_INVALID, "goal %d: term %d: joint reaction goal: the orientation's terms "
+                                   "name different expressed-in bodies", g, tb + k);
+            for (int k = 9; k < 15; ++k)
+                if (!(p->goal_weight[tb + k] >= 0.0))
+                    return set_err(MH_ERR_INVALID, "goal %d: term %d: negative joint reaction measure weight", g,
+                                   tb + k);
+            if (p->goal_column[tb + 15] != 0 && p->goal_column[tb + 15] != 1)
+                return set_err(MH_ERR_INVALID, "goal %d: joint reaction goal: loads frame %d is neither 0 (parent) "
+                               "nor 1 (child)", g, p->goal_column[tb + 15]);
+            const double den = p->goal_weight[tb + 15];
+            if (!(den > 0.0) || !std::isfinite(den))
+                return set_err(MH_ERR_INVALID, "goal %d: joint reaction goal: denominator %g is not positive and "
+                               "finite", g, den);
+            continue;
+        }
         if (G.kind < MH_GOAL_CONTROL || (G.kind > MH_GOAL_MARKER_FINAL && !tracking))
             return set_err(MH_ERR_INVALID, "goal %d: unknown kind %d", g, G.kind);
         if (G.term_begin < 0 || G.term_count < 0 || (int64_t)G.term_begin + G.term_count > p->nterms ||
@@ -2463,6 +2500,15 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     const size_t o_C = A.reserve(sizeof(double) * (size_t)c->G * std::max(1, c->ngoals));
     const size_t o_grad = A.reserve(sizeof(double) * c->n);
     const size_t o_tpart = A.reserve(sizeof(double) * 2 * (size_t)c->G);
+    // joint-reaction goals: k_joint_reaction's lanes and lane values
+    c->njr = 0;
+    for (const mh_goal& G : c->goals) c->njr += G.kind == MH_GOAL_JOINT_REACTION;
+    {
+        const int NDj = c->NI - c->NSL + 2;
+        const int sj = c->fd == MH_FD_CENTRAL ? 2 * NDj + 1 : NDj + 1;
+        c->lanes_jr = Lanes{c->fd, NDj, sj, sj - 1, c->h};
+    }
+    const size_t o_jr = c->njr ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_jr.stride * c->njr) : 0;
     const size_t o_f = A.reserve(sizeof(double) * 4);
     const size_t o_epc = A.reserve(sizeof(double) * (size_t)std::max(1, c->ngoals));   // endpoint costs
     const int npts_iv = c->scheme == MH_HERMITE_SIMPSON ? 3 : 2;
@@ -2662,6 +2708,7 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     c->d_C = (double*)(b + o_C); c->d_grad = (double*)(b + o_grad); c->d_tpart = (double*)(b + o_tpart);
     c->d_f = (double*)(b + o_f);
     c->d_ep = (double*)(b + o_epc);
+    if (c->njr) c->d_jr = (double*)(b + o_jr);
     c->has_marker = false;
     for (int g = 0; g < p->ngoals; ++g) c->has_marker |= p->goals[g].kind == MH_GOAL_MARKER_FINAL;
     if (MT.nm > 0) MT.tab = (const int*)(b + o_mttab);
@@ -3684,6 +3731,14 @@ static void launch_marker_tracking(mh_ctx* c, const Layout& L, int mode) {
             c->d_quad, c->d_C, c->d_grad, c->d_tpart);
 }
 
+// The joint-reaction goals' integrands (mode 0) and their gradient parts too
+// (mode 1), after the other goals' kernels, by the generic interpreter's
+// kernels of the context's size class whatever back end serves g and J.
+static void launch_joint_reaction(mh_ctx* c, int mode) {
+    if (c->njr == 0) return;
+    joint_reaction_backends()[c->size_class].eval(c, c->d_x, mode);
+}
+
 // The objective (partial = false) or this shard's partial of it (partial =
 // true: the integrals over the shard's own mesh intervals, d_quadp, and the
 // endpoint goals -- final time, final marker -- on the shard that owns the
@@ -3702,6 +3757,7 @@ static int eval_f_impl(mh_ctx* c, const double* x, double* f, bool partial) {
     Layout L = make_layout(c, 0, c->G);
     if (c->ngoals > 0) c->be->integrand(c, c->d_x);
     launch_marker_tracking(c, L, 0);   // after k_integrand: the marker-tracking goals' slots
+    launch_joint_reaction(c, 0);       // and the joint-reaction goals'
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)
@@ -3735,6 +3791,7 @@ static int eval_grad_f_impl(mh_ctx* c, const double* x, double* grad, bool parti
         c->be->grad(c, c->d_x);
     }
     launch_marker_tracking(c, L, 1);   // after k_grad: adds to the coordinates' and the t0 / tf entries
+    launch_joint_reaction(c, 1);       // after both: adds to every direction's entry
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)   // after k_grad: adds to the final coordinates' entries
@@ -3772,6 +3829,7 @@ extern "C" int mh_eval_objective_terms(mh_ctx* c, const double* x, double* terms
     Layout L = make_layout(c, 0, c->G);
     c->be->integrand(c, c->d_x);
     launch_marker_tracking(c, L, 0);
+    launch_joint_reaction(c, 0);
     HIPCHK(hipGetLastError());
     if (c->has_marker)
         hipLaunchKernelGGL(k_marker_final, dim3((unsigned)c->ngoals), dim3(128), 0, c->stream, c->M, L, c->GS,
@@ -3811,6 +3869,27 @@ extern "C" int mh_eval_dae(mh_ctx* c, int32_t np, const double* inputs, double* 
     return MH_OK;
 }
 
+extern "C" int mh_eval_joint_reaction(mh_ctx* c, int32_t goal, int32_t np, const double* inputs, double* out) {
+    if (!c || !inputs || !out || np < 0) return set_err(MH_ERR_INVALID, "bad argument");
+    // (c->goals ends with the library's own multiplier term: the problem's goals come first)
+    if (goal < 0 || goal >= (int)c->goals.size() || c->goals[goal].kind != MH_GOAL_JOINT_REACTION)
+        return set_err(MH_ERR_INVALID, "goal %d is not a joint reaction goal", goal);
+    if (np == 0) return MH_OK;
+    HIPCHK(hipSetDevice(c->device));
+    double *din = nullptr, *dout = nullptr;
+    const size_t nin = (size_t)np * (1 + c->NI), nout = (size_t)np * 6;
+    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
+    HIPCHK(hipMalloc(&dout, sizeof(double) * nout));
+    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
+    (void)hipGetLastError();
+    joint_reaction_backends()[c->size_class].probe(c, goal, np, din, dout);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    return MH_OK;
+}
 
 // Path-constraint values of np probe rows [t, states, controls, ...]
 // (sparsity detection of the path-constraint callbacks).

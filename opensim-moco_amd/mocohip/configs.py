@@ -27,7 +27,7 @@ from . import abi
 from .osim import add_reserves
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm,
                       MocoControlBoundConstraint, MocoControlGoal, MocoFrameDistanceConstraint,
-                      MocoInitialActivationGoal,
+                      MocoInitialActivationGoal, MocoJointReactionGoal,
                       FrameReference, MocoAngularVelocityTrackingGoal, MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoMarkerTrackingGoal,
                       MarkersReference, MocoOrientationTrackingGoal, MocoProblem, MocoStateTrackingGoal,
                       MocoTranslationTrackingGoal, PiecewiseLinearFunction)
@@ -1116,3 +1116,118 @@ CONFIGS = {
     "rajagopal18_inverse": rajagopal18_inverse,
     "rajagopal80": rajagopal80,
 }
+
+
+# ---- MocoJointReactionGoal ---------------------------------------------------
+def double_pendulum_joint_reaction(num_mesh_intervals: int = 2, scheme: str = "hermite-simpson",
+                                   fd_scheme: str = "central", dynamics: str = "explicit",
+                                   reaction: bool = True) -> MocoStudy:
+    """The double pendulum (control-effort goal, 0.001) over [0, 1] with three
+    MocoJointReactionGoals on its second pin, j1, after it: "reaction_child"
+    (weight 0.5: the loads on the child frame, all six measures, force-y
+    weighted 2), "reaction_parent" (weight 0.25: the loads on the parent frame
+    expressed in the rotated offset frame "probe" of b0) and "reaction_subset"
+    (the parent loads in ground, moment-z and force-x only, force-x weighted
+    3).  ``reaction`` = False: the same study without them."""
+    m = n_link_pendulum(2)
+    m.add_offset_frame("probe", "b0", (-0.3, 0.1, 0.05), (0.3, -0.6, 0.9))
+    p = MocoProblem(m)
+    p.set_time_bounds(0.0, 1.0)
+    for j, q in (("j0", "q0"), ("j1", "q1")):
+        p.set_state_info(f"/jointset/{j}/{q}/value", (-10, 10))
+        p.set_state_info(f"/jointset/{j}/{q}/speed", (-50, 50))
+    p.set_control_info("/tau0", (-100, 100))
+    p.set_control_info("/tau1", (-100, 100))
+    p.add_goal(MocoControlGoal("control_effort", 0.001))
+    if reaction:
+        p.add_goal(MocoJointReactionGoal("reaction_child", 0.5, joint_path="/jointset/j1", loads_frame="child",
+                                         reaction_weights={"force-y": 2.0}))
+        p.add_goal(MocoJointReactionGoal("reaction_parent", 0.25, joint_path="j1",
+                                         expressed_in_frame_path="/bodyset/b0/probe"))
+        p.add_goal(MocoJointReactionGoal("reaction_subset", 1.0, joint_path="j1",
+                                         expressed_in_frame_path="/ground",
+                                         reaction_measures=["force-x", "moment-z"],
+                                         reaction_weights={"force-x": 3.0}))
+    s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals, transcription_scheme=scheme,
+                      optim_finite_difference_scheme=fd_scheme, multibody_dynamics_mode=dynamics)
+    return MocoStudy(p, s)
+
+
+def spline_knee_weld(num_mesh_intervals: int = 2, fd_scheme: str = "central", dynamics: str = "explicit",
+                     reaction: bool = True) -> MocoStudy:
+    """spline_knee's study (spline and translation axes) with a "brace" of
+    mass 0.4 welded to the shank at (0.02, -0.25, 0.01), rotated by (0.1,
+    -0.2, 0.3), and two MocoJointReactionGoals: "knee_reaction" (the knee's
+    loads on its child, the shank, in the shank's "imu" frame) and
+    "weld_reaction" (the weld's loads on its parent frame).  ``reaction`` =
+    False: the same study without them."""
+    st = spline_knee(num_mesh_intervals, fd_scheme=fd_scheme)
+    m = st.problem.model
+    m.add_body(Body("brace", 0.4, (0.01, -0.03, 0.02), (0.004, 0.003, 0.005, 0, 0, 0)))
+    m.add_joint(Joint("brace_weld", "shank", "brace", [], [], loc_in_parent=(0.02, -0.25, 0.01),
+                      orient_in_parent=(0.1, -0.2, 0.3), loc_in_child=(0.0, 0.05, 0.0)))
+    if reaction:
+        st.problem.add_goal(MocoJointReactionGoal("knee_reaction", 0.5, joint_path="knee", loads_frame="child",
+                                                  expressed_in_frame_path="/bodyset/shank/imu"))
+        st.problem.add_goal(MocoJointReactionGoal("weld_reaction", 2.0, joint_path="brace_weld"))
+    st.solver.multibody_dynamics_mode = dynamics
+    return st
+
+
+def cart_welded_payload(num_mesh_intervals: int = 5) -> MocoStudy:
+    """A cart A (mass 1) on a slider along x with a CoordinateActuator and a
+    payload B (mass 1) welded to it, gravity (10, 0, 0) along the slider, time
+    [0, 1], from rest at 0, control in [-20, 20]: minimize force-x of the weld.
+    The weld carries nothing exactly in free fall: control 0, final position
+    5, final speed 10 (the slider stand-in for testMocoGoals.cpp:364-411, whose
+    PointActuator on a coordinate-free model is not available here)."""
+    m = Model("cart_welded_payload", gravity=(10.0, 0.0, 0.0))
+    m.add_body(Body("A", 1.0, (0, 0, 0), (1, 1, 1, 0, 0, 0)))
+    m.add_body(Body("B", 1.0, (0, 0, 0), (1, 1, 1, 0, 0, 0)))
+    x = Coordinate("x", (-math.inf, math.inf), "translational")
+    m.add_joint(Joint.slider("slider", "ground", "A", x))
+    m.add_joint(Joint("weld", "A", "B", [], [], loc_in_parent=(0.0, 0.5, 0.0)))
+    m.add_coordinate_actuator(CoordinateActuator("push", "x", 1.0, path="/forceset/push"))
+    p = MocoProblem(m)
+    p.set_time_bounds(0.0, 1.0)
+    p.set_state_info("/jointset/slider/x/value", (-20, 20), 0)
+    p.set_state_info("/jointset/slider/x/speed", (-50, 50), 0)
+    p.set_control_info("/forceset/push", (-20, 20))
+    p.add_goal(MocoJointReactionGoal("weld_force", 1.0, joint_path="weld", reaction_measures=["force-x"]))
+    return MocoStudy(p, MocoHipSolver(num_mesh_intervals=num_mesh_intervals))
+
+
+def inverted_pendulum(num_mesh_intervals: int = 20, goal: str = "effort") -> MocoStudy:
+    """exampleMinimizeJointReaction.m:44-106: a body (mass 1, inertia 1) on a
+    pin at the ground origin, joint frame at (-1, 0, 0) of the body, a
+    CoordinateActuator of optimal force 1, time [0, 1], the angle from 0 to pi
+    at rest, control in [-100, 100], convergence tolerance 1e-3.  goal:
+    "effort" (MocoControlGoal) or "reaction" (MocoJointReactionGoal on the pin,
+    its defaults)."""
+    m = Model("inverted_pendulum")
+    m.add_body(Body("body", 1.0, (0, 0, 0), (1, 1, 1, 0, 0, 0)))
+    angle = Coordinate("angle", (-math.inf, math.inf))
+    m.add_joint(Joint.pin("pin", "ground", "body", angle, loc_in_child=(-1, 0, 0)))
+    m.add_coordinate_actuator(CoordinateActuator("actuator", "angle", 1.0, path="/forceset/actuator"))
+    m.add_offset_frame("body_center", "body", (-0.5, 0.0, 0.0))
+    p = MocoProblem(m)
+    p.set_time_bounds(0.0, 1.0)
+    p.set_state_info("/jointset/pin/angle/value", (-10, 10), 0, math.pi)
+    p.set_state_info("/jointset/pin/angle/speed", (-50, 50), 0, 0)
+    p.set_control_info("/forceset/actuator", (-100, 100))
+    if goal == "effort":
+        p.add_goal(MocoControlGoal("effort"))
+    elif goal == "reaction":
+        p.add_goal(MocoJointReactionGoal("reaction", joint_path="pin"))
+    else:
+        raise ValueError(goal)
+    return MocoStudy(p, MocoHipSolver(num_mesh_intervals=num_mesh_intervals, optim_convergence_tolerance=1e-3))
+
+
+def gait10dof18musc_knee_reaction(num_mesh_intervals: int = 200, joint: str = "knee_r", **kw) -> MocoStudy:
+    """gait10dof18musc's study with a MocoJointReactionGoal "knee_reaction"
+    (weight 0.1) after its goals: the loads of ``joint`` on its child frame,
+    all six measures."""
+    st = gait10dof18musc(num_mesh_intervals, **kw)
+    st.problem.add_goal(MocoJointReactionGoal("knee_reaction", 0.1, joint_path=joint, loads_frame="child"))
+    return st

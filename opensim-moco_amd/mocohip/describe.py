@@ -16,7 +16,7 @@ import numpy as np
 from .model import CoordinateActuator, DataTable, DeGrooteFregly2016Muscle
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm, MocoControlBoundConstraint,
                       MocoControlGoal, MocoFinalTimeGoal, MocoFrameDistanceConstraint, MocoInitialActivationGoal,
-                      MocoAngularVelocityTrackingGoal,
+                      MocoAngularVelocityTrackingGoal, MocoJointReactionGoal,
                       MocoMarkerFinalGoal, MocoMarkerTrackingGoal, MocoOrientationTrackingGoal,
                       MocoTranslationTrackingGoal,
                       MocoStateTrackingGoal, MocoSumSquaredStateGoal, PiecewiseLinearFunction)
@@ -185,6 +185,12 @@ def describe(study) -> str:
             paths = g.tracked_frame_paths()
             out.append(" ".join(["goal", kind, _s(g.name), _d(g.weight), _s(g.reference_name()), str(len(paths))]
                                 + [f"{_s(k)} {_d(g.weight_for_frame(k))}" for k in paths]))
+        elif isinstance(g, MocoJointReactionGoal):
+            w = list(g.reaction_weights.items())
+            out.append(" ".join(["goal", "joint_reaction", _s(g.name), _d(g.weight), _s(g.joint_path),
+                                 _s(g.loads_frame), _s(g.expressed_in_frame_path), str(len(g.reaction_measures))]
+                                + [_s(m) for m in g.reaction_measures] + [str(len(w))]
+                                + [f"{_s(k)} {_d(v)}" for k, v in w]))
         elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
             out.append(f"goal aux_derivatives {_s(g.name)} {_d(g.weight)}")
         else:

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import abi
 from .model import CompiledModel, CoordinateActuator, DataTable, \
-    DeGrooteFregly2016Muscle, Model, SpringGeneralizedForce, unit3
+    DeGrooteFregly2016Muscle, Model, SpringGeneralizedForce, body_fixed_xyz, unit3
 from .splines import gcv_interpolating_ppoly
 
 NAN = float("nan")
@@ -391,6 +391,62 @@ class MocoAngularVelocityTrackingGoal(_FrameTrackingGoal):
         return vals
 
 
+@dataclass
+class MocoJointReactionGoal:
+    """MocoJointReactionGoal (Moco/Moco/MocoGoal/MocoJointReactionGoal.{h,cpp}):
+    the integral over the phase of the weighted sum of squares of the chosen
+    reaction measures of one joint, divided by the model's weight (total mass
+    when there is no gravity), times the weight (include/mocohip.h
+    MH_GOAL_JOINT_REACTION).  ``joint_path``: /jointset/<joint> or the joint's
+    name.  ``loads_frame``: "parent" or "child", the joint frame whose body
+    the load is applied to and at whose origin it is taken.
+    ``expressed_in_frame_path``: the frame the load is expressed in (a body,
+    ground or an offset frame; empty: the loads frame).  ``reaction_measures``:
+    any of moment-x, moment-y, moment-z, force-x, force-y, force-z (empty: all
+    six).  ``reaction_weights``: measure -> weight (1 unless given)."""
+    name: str = "joint_reaction"
+    weight: float = 1.0
+    joint_path: str = ""
+    loads_frame: str = "parent"
+    expressed_in_frame_path: str = ""
+    reaction_measures: List[str] = field(default_factory=list)
+    reaction_weights: Dict[str, float] = field(default_factory=dict)
+
+    MEASURES = ("moment-x", "moment-y", "moment-z", "force-x", "force-y", "force-z")
+
+    def set_joint_path(self, path: str):
+        self.joint_path = path
+
+    def set_loads_frame(self, frame: str):
+        self.loads_frame = frame
+
+    def set_expressed_in_frame_path(self, path: str):
+        self.expressed_in_frame_path = path
+
+    def set_reaction_measures(self, measures: Sequence[str]):
+        self.reaction_measures = list(measures)
+
+    def set_weight(self, measure: str, weight: float):
+        self.reaction_weights[measure] = float(weight)
+
+    def measure_weights(self) -> List[float]:
+        """The six weights in MEASURES order: 0 for a measure that was not
+        selected; the reference's error for an unknown measure."""
+        if not self.joint_path:
+            raise ValueError("Expected a joint path, but property joint_path is empty.")
+        if self.loads_frame not in ("parent", "child"):
+            raise ValueError(f"Property 'loads_frame' (in object '{self.name}' of type MocoJointReactionGoal) "
+                             f"has invalid value {self.loads_frame}; expected one of the following:  child  parent.")
+        for m in self.reaction_measures:
+            if m not in self.MEASURES:
+                raise ValueError(f"Reaction measure '{m}' not recognized.")
+        chosen = self.reaction_measures or list(self.MEASURES)
+        w = [0.0] * 6
+        for m in chosen:
+            w[self.MEASURES.index(m)] = float(self.reaction_weights.get(m, 1.0))
+        return w
+
+
 # ------------------------------------------------- functions of time ----
 @dataclass
 class Constant:
@@ -736,6 +792,14 @@ class ProblemRep:
                     raise NotImplementedError(f"{type(g).__name__} with prescribed kinematics "
                                               "(the coordinates are not NLP states)")
                 self._frame_tracking_terms(model, g, gs, gidx, gcol, gw)
+            elif isinstance(g, MocoJointReactionGoal):
+                if kin is not None:
+                    raise NotImplementedError("MocoJointReactionGoal with prescribed kinematics "
+                                              "(the accelerations are not the NLP's)")
+                if problem.parameters:
+                    raise NotImplementedError("MocoJointReactionGoal with MocoParameters "
+                                              "(the load reads the mass properties)")
+                self._joint_reaction_terms(model, g, gs, gidx, gcol, gw)
             elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
                 gs.kind = abi.MH_GOAL_AUX_DERIVATIVES
                 naux = sum(1 for m in model.muscles if not m.ignore_tendon_compliance
@@ -1058,6 +1122,43 @@ class ProblemRep:
                 for c in range(3):   # angular velocity: the frame's location is not used
                     gidx.append(body); gcol.append(ci[c]); gw.append(0.0 if angvel else float(fr[1][c]))
             gidx.append(body); gcol.append(-1); gw.append(w)
+
+    def _joint_reaction_terms(self, model: Model, g: "MocoJointReactionGoal", gs, gidx, gcol, gw):
+        """MocoJointReactionGoal::initializeOnModelImpl: sixteen terms
+        (include/mocohip.h MH_GOAL_JOINT_REACTION) -- R_EO with the
+        expressed-in body, the six measure weights, the loads frame with the
+        denominator."""
+        gs.kind = abi.MH_GOAL_JOINT_REACTION
+        w6 = g.measure_weights()   # (the reference checks the joint path and the loads frame first)
+        joint = next((j for j in model.joints if g.joint_path in (j.name, "/jointset/" + j.name)), None)
+        if joint is None:
+            raise ValueError(f"MocoJointReactionGoal: no joint '{g.joint_path}' in the model")
+        for m, w in zip(g.MEASURES, w6):
+            if w < 0:
+                raise ValueError(f"MocoJointReactionGoal: negative weight {w} of measure '{m}'")
+        child = g.loads_frame == "child"
+        b = self.compiled.body_index[joint.child]
+        if g.expressed_in_frame_path:
+            fr = model.find_frame(g.expressed_in_frame_path)
+            if fr is None:
+                raise ValueError(f"MocoJointReactionGoal: no frame '{g.expressed_in_frame_path}' in the model")
+            e, R = self.compiled.body_index[fr[0]], model.find_frame_orientation(g.expressed_in_frame_path)
+        else:   # the joint's own frame on that side
+            e = self.compiled.body_index[joint.child if child else joint.parent]
+            R = body_fixed_xyz(joint.orient_in_child if child else joint.orient_in_parent)
+        # Model::getTotalMass x |gravity| (the total mass without gravity)
+        den = 0.0
+        for body in model.bodies.values():
+            den += float(body.mass)
+        g0, g1, g2 = (float(v) for v in model.gravity)
+        gmag = math.sqrt((g0 * g0 + g1 * g1) + g2 * g2)
+        if gmag > float(np.finfo(float).eps) ** 0.875:   # SimTK::SignificantReal
+            den *= gmag
+        for k in range(9):
+            gidx.append(b); gcol.append(e); gw.append(float(R[k // 3, k % 3]))
+        for w in w6:
+            gidx.append(b); gcol.append(-1); gw.append(w)
+        gidx.append(b); gcol.append(1 if child else 0); gw.append(den)
 
     @staticmethod
     def _frame_distance_equations(model: Model, pc: "MocoFrameDistanceConstraint", eqs, frame_terms):

@@ -580,6 +580,33 @@ class HipNLP(_NLPBase):
         self._check(self.lib.mh_eval_objective_terms(self.ctx, abi.dptr(x), abi.dptr(out), C.byref(k)))
         return out[:int(k.value)]
 
+    def eval_joint_reaction(self, goal: int, inputs: np.ndarray) -> np.ndarray:
+        """Rows [t, point inputs] (as eval_dae) -> [moment x, y, z, force x,
+        y, z] of joint-reaction goal ``goal`` (its index among the problem's
+        goals) in the goal's frames (mh_eval_joint_reaction)."""
+        inputs = np.ascontiguousarray(inputs, float)
+        npts = inputs.shape[0]
+        assert inputs.shape[1] == 1 + self.NI
+        out = np.empty((npts, 6))
+        self._check(self._fn("eval_joint_reaction")(self.ctx, int(goal), npts, abi.dptr(inputs), abi.dptr(out)))
+        return out
+
+    def joint_reaction(self, trajectory, goal_name: str) -> np.ndarray:
+        """[grid points, 6]: the reaction load of the MocoJointReactionGoal
+        named ``goal_name`` at every grid point of ``trajectory`` (a
+        MocoTrajectory on this NLP's grid, or an iterate x): moment x, y, z
+        and force x, y, z on the goal's loads frame, expressed in its
+        expressed-in frame -- what the reference's example computes from its
+        solution after the solve."""
+        names = list(self.rep.goal_names)
+        if goal_name not in names:
+            raise ValueError(f"no goal '{goal_name}' in the problem")
+        x = trajectory.to_iterate(self) if hasattr(trajectory, "to_iterate") else np.asarray(trajectory, float)
+        from .trajectory import nlp_grid
+        grid = nlp_grid(self)
+        t = x[0] + (x[1] - x[0]) * grid
+        return self.eval_joint_reaction(names.index(goal_name), np.column_stack([t, self.point_inputs(x)]))
+
     def eval_g(self, x, new_x=True):
         x = np.ascontiguousarray(x, float)
         g = np.empty(max(self.row_end - self.row_begin, 1))
