@@ -509,7 +509,66 @@ enum mh_goal_kind {
      * point, added to the entries the other goals wrote.  Goals of this kind
      * on one problem share the evaluations.  mh_batch_* accepts contexts with
      * such goals and never reads them, as for every other goal. */
-    MH_GOAL_JOINT_REACTION = 14
+    MH_GOAL_JOINT_REACTION = 14,
+    /* MocoAccelerationTrackingGoal (MocoAccelerationTrackingGoal.cpp:96-120):
+     * weight * duration * quadrature over every grid point of
+     *     L = sum over the tracked frames f, in order, of
+     *         w_f * |a_G(origin of frame f) - ref_f(t)|^2
+     * a_G = the linear acceleration of the frame's origin in ground, expressed
+     * in ground: the kinematic acceleration (gravity is not added to it; an
+     * accelerometer's a - g is a follow-up).  `table` = the reference.  Four
+     * consecutive terms per frame, kind 9's layout, goal_index = the frame's
+     * body in all of them (-1 = ground, a = 0).  Terms 0-2: goal_weight = the
+     * origin's location in its body, goal_column = the table's
+     * <frame>/acceleration_x / _y / _z column.  Term 3: goal_column = -1,
+     * goal_weight = w_f (>= 0).  mh_goal.exponent is unused.
+     * Accelerations udot: with implicit multibody dynamics the iterate's
+     * acceleration variables; with explicit dynamics the udot that the DAE
+     * solves at the point (M udot = f).  Not with prescribed kinematics and
+     * not with MocoParameters (MH_ERR_UNSUPPORTED, as kind 14).  Kinematic
+     * constraints (couplers) are accepted.
+     * Per frame, each operation rounded on its own (no fused multiply-add),
+     * every 3x3 product entry and matrix-vector entry summed as
+     * (a0 b0 + a1 b1) + a2 b2, every cross product entry a single difference
+     * of two products, x_c over the three components:
+     *   1. At the ground: pose = identity, V = (omega, v) = 0 and
+     *      A = (alpha, a0) = 0: spatial velocity and acceleration in ground
+     *      about the ground origin, the convention of the DAE's forward pass
+     *      but with zero base acceleration (no gravity term).
+     *   2. Walk the body's ancestor chain root first.  Per body, with R_GF,
+     *      R_cur and the joint origin oM exactly the position stage's (kinds
+     *      7-12), Vpar = V on entry, and for an axis whose function of
+     *      coordinate j is not MH_FN_CONSTANT: d1, d2 = the function's first
+     *      and second derivative, thd = d1 * u_j,
+     *      thdd = (d2 * u_j) * u_j + d1 * udot_j.
+     *      a. every translation axis, in axis order:
+     *           s = R_GF dir;  e = Vpar.omega x s
+     *           v_c  = v_c + s_c * thd
+     *           a0_c = a0_c + (e_c * thd + s_c * thdd)
+     *      b. then every rotation axis, in axis order, with the running V:
+     *           w = (R_GF R_cur) dir;  s = oM x w
+     *           f = omega x w;  e = (omega x s) + (v x w)
+     *           omega_c = omega_c + w_c * thd;  v_c = v_c + s_c * thd
+     *           alpha_c = alpha_c + (f_c * thd + w_c * thdd)
+     *           a0_c    = a0_c + (e_c * thd + s_c * thdd)
+     *         (f and e from V before this axis's own update.)
+     *   3. r = p_GB + R_GB location;  p = v + omega x r (the origin's velocity)
+     *      a_c = (a0_c + (alpha x r)_c) + (omega x p)_c
+     *   4. d_c = a_c - ref_c(t);  L = L + w_f * ((d_0 d_0 + d_1 d_1) + d_2 d_2)
+     *      (from L = 0.0)
+     * that is a = a0 + alpha x r + omega x (v + omega x r), with the spline
+     * terms d2 u^2 and the velocity-product terms of the axes inside one body.
+     * Gradient: finite-difference quotients of the whole integrand with
+     * k_grad's formulas, one evaluation per direction and grid point, added to
+     * the entries the other goals wrote.  Explicit dynamics: over t0, tf and
+     * every point input but the slacks (one DAE evaluation per lane; external
+     * loads make udot depend on t).  Implicit dynamics: over t0, tf and, for
+     * every coordinate that is the argument of a non-constant function on an
+     * axis of a body on a tracked frame's chain, its value, its speed and its
+     * acceleration variable; every other entry keeps its bits.  Goals of this
+     * kind on one problem share the evaluations.  mh_batch_* accepts contexts
+     * with such goals and never reads them, as for every other goal. */
+    MH_GOAL_ACCELERATION_TRACKING = 15
 };
 typedef struct mh_goal {
     int32_t kind;
@@ -944,6 +1003,15 @@ int mh_eval_dae(mh_ctx* ctx, int32_t npoints, const double* inputs,
  * force x, y, z, on the goal's loads frame and expressed in its expressed-in
  * frame (r of MH_GOAL_JOINT_REACTION, step 3).  Synchronous. */
 int mh_eval_joint_reaction(mh_ctx* ctx, int32_t goal, int32_t npoints, const double* inputs,
+        double* out);
+/* The accelerations that goal `goal` (of kind MH_GOAL_ACCELERATION_TRACKING;
+ * any other goal: MH_ERR_INVALID) tracks, at npoints rows [time, NI point
+ * inputs], as for mh_eval_joint_reaction: out holds 3 doubles per row and
+ * tracked frame, out[row][frame][xyz], the linear acceleration of the frame's
+ * origin in ground (a of MH_GOAL_ACCELERATION_TRACKING, step 3; udot from the
+ * row's acceleration inputs or, with explicit dynamics, from the DAE at the
+ * row).  npoints <= 0: MH_ERR_INVALID.  Synchronous. */
+int mh_eval_frame_accelerations(mh_ctx* ctx, int32_t goal, int32_t npoints, const double* inputs,
         double* out);
 /* Path-constraint probe, the counterpart of mh_eval_dae for the path
  * callback: the npath path-equation values of npoints probe rows [time, point

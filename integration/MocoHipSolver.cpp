@@ -32,6 +32,7 @@
 #include <OpenSim/Moco/MocoGoal/MocoInitialActivationGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoMarkerFinalGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoMarkerTrackingGoal.h>
+#include <OpenSim/Moco/MocoGoal/MocoAccelerationTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoAngularVelocityTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoJointReactionGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoOrientationTrackingGoal.h>
@@ -523,7 +524,8 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
                 prob.model.add_table(toTable(hg.table, mref.getMarkerTable().flatten(), 5));
         } else if (dynamic_cast<const MocoTranslationTrackingGoal*>(&g) ||
                    dynamic_cast<const MocoOrientationTrackingGoal*>(&g) ||
-                   dynamic_cast<const MocoAngularVelocityTrackingGoal*>(&g)) {
+                   dynamic_cast<const MocoAngularVelocityTrackingGoal*>(&g) ||
+                   dynamic_cast<const MocoAccelerationTrackingGoal*>(&g)) {
             // The goals keep their splines and an in-memory reference table
             // private, so the frame data is computed again from what is
             // public: the states reference (as initializeOnModelImpl does,
@@ -536,17 +538,27 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
             // Goal.cpp:98-111) -- goes in as a model table, splined as
             // GCVSplineSet(table) does (degree 5); the frames as offset
             // frames with their orientation; mhb::make_rep runs the checks.
+            // A MocoAccelerationTrackingGoal (<path>/acceleration_x|y|z) has a
+            // reference file only: the class has no states_reference property.
+            const bool accel = dynamic_cast<const MocoAccelerationTrackingGoal*>(&g) != nullptr;
             const bool orient = dynamic_cast<const MocoOrientationTrackingGoal*>(&g) != nullptr;
             const bool angvel = dynamic_cast<const MocoAngularVelocityTrackingGoal*>(&g) != nullptr;
             hg.kind = orient ? mhb::Goal::ORIENTATION_TRACKING
-                    : (angvel ? mhb::Goal::ANGULAR_VELOCITY_TRACKING : mhb::Goal::TRANSLATION_TRACKING);
-            const std::string what = orient ? "rotation" : (angvel ? "angular_velocity" : "translation");
+                    : (angvel ? mhb::Goal::ANGULAR_VELOCITY_TRACKING
+                              : (accel ? mhb::Goal::ACCELERATION_TRACKING : mhb::Goal::TRANSLATION_TRACKING));
+            const std::string what =
+                    orient ? "rotation" : (angvel ? "angular_velocity" : (accel ? "acceleration" : "translation"));
             hg.table = what + "_reference_" + g.getName();
             const auto& pathsProp = g.getPropertyByName("frame_paths");
             std::vector<std::string> paths;
             for (int i = 0; i < pathsProp.size(); ++i) paths.push_back(pathsProp.getValue<std::string>(i));
             const std::string file = g.getPropertyByName(what + "_reference_file").getValue<std::string>();
-            const auto& statesRef = g.getPropertyByName("states_reference").getValue<TableProcessor>();
+            OPENSIM_THROW_IF(accel && file.empty(), Exception,
+                    "MocoHipSolver: goal '{}': an acceleration reference set in memory cannot be read back from the "
+                    "goal; give it as a file", g.getName());
+            const TableProcessor noStates;
+            const auto& statesRef =
+                    accel ? noStates : g.getPropertyByName("states_reference").getValue<TableProcessor>();
             std::vector<double> times;
             std::vector<std::vector<SimTK::Rotation>> rotations;   // [row][frame]
             std::vector<std::vector<SimTK::Vec3>> positions;       // or angular velocities
@@ -559,7 +571,9 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
                         OPENSIM_THROW_IF(it == labels.end(), Exception,
                                 "Expected frame_paths to match one of the column labels in the {} reference, but "
                                 "frame path '{}' not found in the reference labels.",
-                                orient ? "rotation" : (angvel ? "angular velocity" : "translation"), path);
+                                orient ? "rotation"
+                                       : (angvel ? "angular velocity" : (accel ? "acceleration" : "translation")),
+                                path);
                         cols.push_back((int)(it - labels.begin()));
                     }
                     return cols;
@@ -608,10 +622,11 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
             std::vector<std::string> labels;
             static const char* const psfx[3] = {"position_x", "position_y", "position_z"};
             static const char* const wsfx[3] = {"angular_velocity_x", "angular_velocity_y", "angular_velocity_z"};
+            static const char* const asfx[3] = {"acceleration_x", "acceleration_y", "acceleration_z"};
             for (const auto& path : paths)
                 for (int c = 0; c < per; ++c)
                     labels.push_back(orient ? path + "/quaternion_e" + std::to_string(c)
-                                            : path + "/" + (angvel ? wsfx[c] : psfx[c]));
+                                            : path + "/" + (angvel ? wsfx[c] : (accel ? asfx[c] : psfx[c])));
             TimeSeriesTable flat;
             std::vector<std::string> sorted(paths);
             std::sort(sorted.begin(), sorted.end());

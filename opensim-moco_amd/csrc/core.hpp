@@ -2208,7 +2208,8 @@ __host__ __device__ __forceinline__ bool goal_tracked_items(int kind) {
 // integrand and gradient k_marker_tracking writes into the same slots.  The
 // joint-reaction goal (kind 14) is an integral goal: goal_integrand gives 0.0
 // for it, and k_joint_reaction / k_joint_reaction_grad write its slot and add
-// its gradient after k_integrand / k_grad.
+// its gradient after k_integrand / k_grad.  The acceleration-tracking goal
+// (kind 15) likewise, by k_accel_tracking / k_accel_tracking_grad.
 __host__ __device__ __forceinline__ bool goal_integral(int kind) {
     return kind != MH_GOAL_FINAL_TIME && kind != MH_GOAL_MARKER_FINAL && !goal_tracked_items(kind);
 }
@@ -2591,6 +2592,15 @@ struct mh_ctx {
     int njr = 0;
     Lanes lanes_jr{};
     double* d_jr = nullptr;
+    // acceleration-tracking goals (kind 15): their count, the lanes of
+    // k_accel_tracking in gradient mode (ND = NI - NSL + 2), its lane values
+    // [G][stride][nat] and the directions that can change a goal's integrand
+    // [ND] (implicit dynamics: t0, tf and the tracked chains' coordinates,
+    // speeds and acceleration variables; explicit: all)
+    int nat = 0;
+    Lanes lanes_at{};
+    double* d_at = nullptr;
+    const int* d_at_live = nullptr;
     bool use_roles = false;        // MOCOHIP_ROLES=1: k_role (+ k_couple) for the Jacobian lanes
     int role_threads = 256;        // k_role workgroup size (MOCOHIP_ROLE_THREADS: 64..512)
     int iv_threads = 1024;         // k_interval workgroup size, Jacobian lanes (MOCOHIP_IV_THREADS: 256..1024)
@@ -3067,6 +3077,15 @@ struct JointReactionBackend {
     void (*probe)(mh_ctx*, int goal, int np, const double* in, double* out);
 };
 const JointReactionBackend* joint_reaction_backends();
+// The acceleration-tracking goals' kernels (accel_tracking.hip), selected and
+// kept apart in the same way.  eval: the goals' integrands (mode 0) or
+// integrands and gradient parts (mode 1); probe: mh_eval_frame_accelerations'
+// rows.  Each entry picks the instantiation of the context's dynamics mode.
+struct AccelTrackingBackend {
+    void (*eval)(mh_ctx*, const double* x, int mode);
+    void (*probe)(mh_ctx*, int goal, int np, const double* in, double* out);
+};
+const AccelTrackingBackend* accel_tracking_backends();
 // A model-specialized back end (generated/gen_<model>.hip): the task kernels
 // (default) and the one-lane-per-DAE kernel (MOCOHIP_BACKEND=lane), for the
 // model structure match() accepts (multibody dynamics mode and prescribed

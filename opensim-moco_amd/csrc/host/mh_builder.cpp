@@ -879,19 +879,29 @@ void make_rep(const Problem& P, ProblemRep& R) {
         }
         case Goal::TRANSLATION_TRACKING:
         case Goal::ANGULAR_VELOCITY_TRACKING:
+        case Goal::ACCELERATION_TRACKING:
         case Goal::ORIENTATION_TRACKING: {
             // MocoTranslationTrackingGoal / MocoOrientationTrackingGoal::
             // initializeOnModelImpl (problem.py _frame_tracking_terms): four
             // terms per tracked frame (as a marker's), or ten (R_BO, the
             // quaternion columns, the weight); angular velocity: four, the
-            // first three with the columns and zero weights
+            // first three with the columns and zero weights; acceleration:
+            // four, as a translation's with the acceleration columns
             const bool orient = g.kind == Goal::ORIENTATION_TRACKING;
             const bool angvel = g.kind == Goal::ANGULAR_VELOCITY_TRACKING;
+            const bool accel = g.kind == Goal::ACCELERATION_TRACKING;
             const std::string cls = orient ? "MocoOrientationTrackingGoal"
-                                  : (angvel ? "MocoAngularVelocityTrackingGoal" : "MocoTranslationTrackingGoal");
-            if (presc) fail(cls + " with prescribed kinematics (the coordinates are not NLP states)");
+                                  : (angvel ? "MocoAngularVelocityTrackingGoal"
+                                            : (accel ? "MocoAccelerationTrackingGoal" : "MocoTranslationTrackingGoal"));
+            if (presc)
+                fail(cls + (accel ? " with prescribed kinematics (the accelerations are not the NLP's)"
+                                  : " with prescribed kinematics (the coordinates are not NLP states)"));
+            if (accel && !P.parameters.empty())
+                fail("MocoAccelerationTrackingGoal with MocoParameters (the goals' gradient along a parameter is "
+                     "defined as 0)");
             gs.kind = orient ? MH_GOAL_ORIENTATION_TRACKING
-                    : (angvel ? MH_GOAL_ANGULAR_VELOCITY_TRACKING : MH_GOAL_TRANSLATION_TRACKING);
+                    : (angvel ? MH_GOAL_ANGULAR_VELOCITY_TRACKING
+                              : (accel ? MH_GOAL_ACCELERATION_TRACKING : MH_GOAL_TRANSLATION_TRACKING));
             std::vector<std::string> labels;
             for (auto& kv : g.weights) labels.push_back(kv.first);
             std::sort(labels.begin(), labels.end());   // checkRedundantLabels
@@ -904,6 +914,7 @@ void make_rep(const Problem& P, ProblemRep& R) {
             static const char* const psfx[3] = {"position_x", "position_y", "position_z"};
             static const char* const qsfx[4] = {"quaternion_e0", "quaternion_e1", "quaternion_e2", "quaternion_e3"};
             static const char* const wsfx[3] = {"angular_velocity_x", "angular_velocity_y", "angular_velocity_z"};
+            static const char* const asfx[3] = {"acceleration_x", "acceleration_y", "acceleration_z"};
             for (auto& kv : g.weights) {
                 std::string body_name;
                 double loc[3], R_BO[9];
@@ -914,7 +925,7 @@ void make_rep(const Problem& P, ProblemRep& R) {
                 const int body = R.cm.index_of_body(body_name);
                 int ci[4] = {-1, -1, -1, -1};
                 for (int c = 0; c < (orient ? 4 : 3); ++c) {
-                    const std::string col = kv.first + "/" + (orient ? qsfx[c] : (angvel ? wsfx[c] : psfx[c]));
+                    const std::string col = kv.first + "/" + (orient ? qsfx[c] : (angvel ? wsfx[c] : (accel ? asfx[c] : psfx[c])));
                     auto it = std::find(cols.begin(), cols.end(), col);
                     if (it == cols.end()) fail("reference table " + g.table + " has no column '" + col + "'");
                     ci[c] = (int)(it - cols.begin());
@@ -1503,10 +1514,11 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
                 g.name = t.s(); g.weight = t.d(); g.table = t.s(); g.allow_unused_references = t.i() != 0;
                 g.weights = read_weights(t);
             } else if (kind == "translation_tracking" || kind == "orientation_tracking" ||
-                       kind == "angular_velocity_tracking") {
+                       kind == "angular_velocity_tracking" || kind == "acceleration_tracking") {
                 g.kind = kind == "translation_tracking" ? Goal::TRANSLATION_TRACKING
                        : (kind == "orientation_tracking" ? Goal::ORIENTATION_TRACKING
-                                                         : Goal::ANGULAR_VELOCITY_TRACKING);
+                          : (kind == "acceleration_tracking" ? Goal::ACCELERATION_TRACKING
+                                                             : Goal::ANGULAR_VELOCITY_TRACKING));
                 g.name = t.s(); g.weight = t.d(); g.table = t.s();
                 g.weights = read_weights(t);
             } else if (kind == "joint_reaction") {

@@ -248,20 +248,22 @@ struct VariableInfo {
 struct Goal {
     enum Kind { CONTROL, STATE_TRACKING, FINAL_TIME, SUM_SQUARED_STATE, INITIAL_ACTIVATION, MARKER_FINAL,
                 AUX_DERIVATIVES, MARKER_TRACKING, TRANSLATION_TRACKING, ORIENTATION_TRACKING,
-                ANGULAR_VELOCITY_TRACKING, JOINT_REACTION };
+                ANGULAR_VELOCITY_TRACKING, JOINT_REACTION, ACCELERATION_TRACKING };
     Kind kind = CONTROL;
     std::string name;
     double weight = 1.0;
     int exponent = 2;
     // control / state weights; marker tracking: the reference's labels with
     // their weights, by reference index; translation / orientation / angular
-    // velocity tracking: the tracked frame paths with their weights, in order
+    // velocity / acceleration tracking: the tracked frame paths with their
+    // weights, in order
     std::vector<std::pair<std::string, double>> weights;
     // state tracking reference; marker tracking: the flattened markers table
     // (columns <label>_1, _2, _3), one of the model's tables; translation /
     // orientation tracking: the flattened frame table (columns
     // <path>/position_x|y|z, <path>/quaternion_e0..3 or
-    // <path>/angular_velocity_x|y|z)
+    // <path>/angular_velocity_x|y|z; acceleration tracking:
+    // <path>/acceleration_x|y|z)
     std::string table;
     bool allow_unused_references = false;                   // marker tracking
     std::string mode = "endpoint_constraint";               // initial activation

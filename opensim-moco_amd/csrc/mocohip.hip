@@ -1966,6 +1966,31 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
                                "finite", g, den);
             continue;
         }
+        if (G.kind == MH_GOAL_ACCELERATION_TRACKING) {
+            // four terms per frame (include/mocohip.h), kind 9's layout: the
+            // origin's location with the table's columns, then the weight
+            if (G.term_begin < 0 || G.term_count < 0 || G.term_count % 4 != 0 ||
+                    (int64_t)G.term_begin + G.term_count > p->nterms)
+                return set_err(MH_ERR_INVALID, "goal %d: acceleration tracking goal needs four terms per frame", g);
+            if (c->presc)
+                return set_err(MH_ERR_UNSUPPORTED, "goal %d: acceleration tracking goal with prescribed kinematics",
+                               g);
+            if (p->nparameters > 0)
+                return set_err(MH_ERR_UNSUPPORTED, "goal %d: acceleration tracking goal with MocoParameters", g);
+            if (G.table < 0 || G.table >= M.ntables) return set_err(MH_ERR_INVALID, "goal %d: bad table", g);
+            for (int k = G.term_begin; k < G.term_begin + G.term_count; ++k) {
+                const int ti = (k - G.term_begin) % 4, idx = p->goal_index[k];
+                if (idx < -1 || idx >= M.nbodies)
+                    return set_err(MH_ERR_INVALID, "goal %d: term %d index %d out of range", g, k, idx);
+                if (idx != p->goal_index[k - ti])
+                    return set_err(MH_ERR_INVALID, "goal %d: term %d: a frame's terms name different bodies", g, k);
+                if (ti < 3 && (p->goal_column[k] < 0 || p->goal_column[k] >= M.tables[G.table].ncol))
+                    return set_err(MH_ERR_INVALID, "goal %d: term %d column out of range", g, k);
+                if (ti == 3 && !(p->goal_weight[k] >= 0.0))
+                    return set_err(MH_ERR_INVALID, "goal %d: term %d: negative frame weight", g, k);
+            }
+            continue;
+        }
         if (G.kind < MH_GOAL_CONTROL || (G.kind > MH_GOAL_MARKER_FINAL && !tracking))
             return set_err(MH_ERR_INVALID, "goal %d: unknown kind %d", g, G.kind);
         if (G.term_begin < 0 || G.term_count < 0 || (int64_t)G.term_begin + G.term_count > p->nterms ||
@@ -2333,6 +2358,38 @@ static int kinematics_tables(mh_ctx* c, const mh_model& M, const std::vector<int
     return MH_OK;
 }
 
+// The directions of k_accel_tracking's lanes (dir 0 = t0, 1 = tf, 2 + i = point
+// input i; ND = NI - NSL + 2) that can change an acceleration-tracking goal's
+// integrand.  Explicit dynamics: all (udot depends on every input).  Implicit:
+// t0, tf and, for every coordinate that is the argument of a non-constant
+// function on an axis of a body on a tracked frame's ancestor chain, its value,
+// its speed and its acceleration variable.
+static std::vector<int> accel_tracking_live(const mh_ctx* c, const mh_problem* p) {
+    const mh_model& M = p->model;
+    const int ND = c->NI - c->NSL + 2;
+    const bool implicit = c->NACC > 0;   // (c->M is filled later)
+    std::vector<int> live(ND, implicit ? 0 : 1);
+    if (!implicit) return live;
+    live[0] = live[1] = 1;
+    std::vector<char> on(M.nbodies, 0);
+    for (int g = 0; g < p->ngoals; ++g) {
+        const mh_goal& G = p->goals[g];
+        if (G.kind != MH_GOAL_ACCELERATION_TRACKING) continue;
+        for (int k = G.term_begin; k < G.term_begin + G.term_count; k += 4)
+            for (int b = p->goal_index[k], n = 0; b >= 0 && n <= M.nbodies; b = M.bodies[b].parent, ++n) on[b] = 1;
+    }
+    for (int b = 0; b < M.nbodies; ++b) {
+        if (!on[b]) continue;
+        const mh_body& B = M.bodies[b];
+        for (int a = B.axis_begin; a < B.axis_begin + B.axis_count; ++a) {
+            const mh_function& F = M.functions[M.axes[a].func];
+            if (F.kind == MH_FN_CONSTANT) continue;
+            live[2 + F.coord] = live[2 + M.nq + F.coord] = live[2 + c->NS + c->NC + F.coord] = 1;
+        }
+    }
+    return live;
+}
+
 extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out) {
     if (!p || !o || !out) return set_err(MH_ERR_INVALID, "null argument");
     *out = nullptr;
@@ -2509,6 +2566,17 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
         c->lanes_jr = Lanes{c->fd, NDj, sj, sj - 1, c->h};
     }
     const size_t o_jr = c->njr ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_jr.stride * c->njr) : 0;
+    // acceleration-tracking goals: k_accel_tracking's lanes, lane values and
+    // live directions (the same lanes as the joint-reaction goals')
+    c->nat = 0;
+    for (const mh_goal& G : c->goals) c->nat += G.kind == MH_GOAL_ACCELERATION_TRACKING;
+    c->lanes_at = c->lanes_jr;
+    const size_t o_at = c->nat ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_at.stride * c->nat) : 0;
+    size_t o_atlive = 0;
+    if (c->nat) {
+        const std::vector<int> live = accel_tracking_live(c.get(), p);
+        o_atlive = A.put(live.data(), live.size());
+    }
     const size_t o_f = A.reserve(sizeof(double) * 4);
     const size_t o_epc = A.reserve(sizeof(double) * (size_t)std::max(1, c->ngoals));   // endpoint costs
     const int npts_iv = c->scheme == MH_HERMITE_SIMPSON ? 3 : 2;
@@ -2709,6 +2777,10 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     c->d_f = (double*)(b + o_f);
     c->d_ep = (double*)(b + o_epc);
     if (c->njr) c->d_jr = (double*)(b + o_jr);
+    if (c->nat) {
+        c->d_at = (double*)(b + o_at);
+        c->d_at_live = (const int*)(b + o_atlive);
+    }
     c->has_marker = false;
     for (int g = 0; g < p->ngoals; ++g) c->has_marker |= p->goals[g].kind == MH_GOAL_MARKER_FINAL;
     if (MT.nm > 0) MT.tab = (const int*)(b + o_mttab);
@@ -3739,6 +3811,12 @@ static void launch_joint_reaction(mh_ctx* c, int mode) {
     joint_reaction_backends()[c->size_class].eval(c, c->d_x, mode);
 }
 
+// The acceleration-tracking goals' likewise, after the joint-reaction goals'.
+static void launch_accel_tracking(mh_ctx* c, int mode) {
+    if (c->nat == 0) return;
+    accel_tracking_backends()[c->size_class].eval(c, c->d_x, mode);
+}
+
 // The objective (partial = false) or this shard's partial of it (partial =
 // true: the integrals over the shard's own mesh intervals, d_quadp, and the
 // endpoint goals -- final time, final marker -- on the shard that owns the
@@ -3758,6 +3836,7 @@ static int eval_f_impl(mh_ctx* c, const double* x, double* f, bool partial) {
     if (c->ngoals > 0) c->be->integrand(c, c->d_x);
     launch_marker_tracking(c, L, 0);   // after k_integrand: the marker-tracking goals' slots
     launch_joint_reaction(c, 0);       // and the joint-reaction goals'
+    launch_accel_tracking(c, 0);       // and the acceleration-tracking goals'
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)
@@ -3792,6 +3871,7 @@ static int eval_grad_f_impl(mh_ctx* c, const double* x, double* grad, bool parti
     }
     launch_marker_tracking(c, L, 1);   // after k_grad: adds to the coordinates' and the t0 / tf entries
     launch_joint_reaction(c, 1);       // after both: adds to every direction's entry
+    launch_accel_tracking(c, 1);       // after the three: adds to its live directions' entries
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)   // after k_grad: adds to the final coordinates' entries
@@ -3830,6 +3910,7 @@ extern "C" int mh_eval_objective_terms(mh_ctx* c, const double* x, double* terms
     c->be->integrand(c, c->d_x);
     launch_marker_tracking(c, L, 0);
     launch_joint_reaction(c, 0);
+    launch_accel_tracking(c, 0);
     HIPCHK(hipGetLastError());
     if (c->has_marker)
         hipLaunchKernelGGL(k_marker_final, dim3((unsigned)c->ngoals), dim3(128), 0, c->stream, c->M, L, c->GS,
@@ -3883,6 +3964,28 @@ extern "C" int mh_eval_joint_reaction(mh_ctx* c, int32_t goal, int32_t np, const
     HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
     (void)hipGetLastError();
     joint_reaction_backends()[c->size_class].probe(c, goal, np, din, dout);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    return MH_OK;
+}
+extern "C" int mh_eval_frame_accelerations(mh_ctx* c, int32_t goal, int32_t np, const double* inputs, double* out) {
+    if (!c || !inputs || !out) return set_err(MH_ERR_INVALID, "bad argument");
+    if (goal < 0 || goal >= (int)c->goals.size() || c->goals[goal].kind != MH_GOAL_ACCELERATION_TRACKING)
+        return set_err(MH_ERR_INVALID, "goal %d is not an acceleration tracking goal", goal);
+    if (np <= 0) return set_err(MH_ERR_INVALID, "mh_eval_frame_accelerations: %d rows", np);
+    const int nf = c->goals[goal].term_count / 4;
+    if (nf == 0) return MH_OK;
+    HIPCHK(hipSetDevice(c->device));
+    double *din = nullptr, *dout = nullptr;
+    const size_t nin = (size_t)np * (1 + c->NI), nout = (size_t)np * nf * 3;
+    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
+    HIPCHK(hipMalloc(&dout, sizeof(double) * nout));
+    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
+    (void)hipGetLastError();
+    accel_tracking_backends()[c->size_class].probe(c, goal, np, din, dout);
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));

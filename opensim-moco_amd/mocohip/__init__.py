@@ -7,7 +7,7 @@ the model compiler that feeds the C ABI.
 from .model import (Axis, Body, Coordinate, CoordinateActuator, DataTable,  # noqa: F401
                     DeGrooteFregly2016Muscle, ExternalForce, Function, Joint,
                     Model, PathPoint)
-from .problem import (MocoAngularVelocityTrackingGoal, MocoBounds, MocoControlGoal,  # noqa: F401
+from .problem import (MocoAccelerationTrackingGoal, MocoAngularVelocityTrackingGoal, MocoBounds, MocoControlGoal,  # noqa: F401
                       MocoFinalTimeGoal, MocoJointReactionGoal, MocoOrientationTrackingGoal, MocoProblem, MocoStateTrackingGoal,
                       MocoSumSquaredStateGoal, MocoTranslationTrackingGoal)
 from .solver import HipNLP, MocoHipSolver, MocoStudy  # noqa: F401

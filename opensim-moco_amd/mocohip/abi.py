@@ -24,6 +24,7 @@ MH_GOAL_MARKER_TRACKING = 7   # 6: the library's own multiplier term
 MH_GOAL_TRANSLATION_TRACKING, MH_GOAL_ORIENTATION_TRACKING = 9, 10   # 8: not assigned
 MH_GOAL_ANGULAR_VELOCITY_TRACKING = 12   # 11: not assigned
 MH_GOAL_JOINT_REACTION = 14   # 13: not assigned
+MH_GOAL_ACCELERATION_TRACKING = 15
 MH_HERMITE_SIMPSON, MH_TRAPEZOIDAL = 0, 1
 MH_DYNAMICS_EXPLICIT, MH_DYNAMICS_IMPLICIT = 0, 1
 MH_FD_CENTRAL, MH_FD_FORWARD, MH_FD_BACKWARD = 0, 1, 2
@@ -249,6 +250,7 @@ MOCOHIP_SYMBOLS = {
     "mh_tnlp_eval_jac_g_device": (i32, [C.c_void_p, C.c_void_p, i32, C.c_void_p]),
     "mh_eval_dae": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
     "mh_eval_joint_reaction": (i32, [C.c_void_p, i32, i32, P(f64), P(f64)]),
+    "mh_eval_frame_accelerations": (i32, [C.c_void_p, i32, i32, P(f64), P(f64)]),
     "mh_eval_path": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
     "mh_set_timing": (i32, [C.c_void_p, i32]),
     "mh_get_backend_flags": (i32, [C.c_void_p, C.c_char_p, i32]),

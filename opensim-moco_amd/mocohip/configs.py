@@ -27,7 +27,7 @@ from . import abi
 from .osim import add_reserves
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm,
                       MocoControlBoundConstraint, MocoControlGoal, MocoFrameDistanceConstraint,
-                      MocoInitialActivationGoal, MocoJointReactionGoal,
+                      MocoAccelerationTrackingGoal, MocoInitialActivationGoal, MocoJointReactionGoal,
                       FrameReference, MocoAngularVelocityTrackingGoal, MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoMarkerTrackingGoal,
                       MarkersReference, MocoOrientationTrackingGoal, MocoProblem, MocoStateTrackingGoal,
                       MocoTranslationTrackingGoal, PiecewiseLinearFunction)
@@ -1231,3 +1231,72 @@ def gait10dof18musc_knee_reaction(num_mesh_intervals: int = 200, joint: str = "k
     st = gait10dof18musc(num_mesh_intervals, **kw)
     st.problem.add_goal(MocoJointReactionGoal("knee_reaction", 0.1, joint_path=joint, loads_frame="child"))
     return st
+
+
+# ---- MocoAccelerationTrackingGoal ----------------------------------------------
+def accelerations_from_coordinates(m: Model, paths, times, coordinate_columns) -> FrameReference:
+    """A reference for a MocoAccelerationTrackingGoal from coordinate data
+    alone: the second time difference (numpy.gradient applied twice, second-
+    order edges) of the frames' origin positions by forward kinematics at the
+    rows.  Data to track, not a check of anything."""
+    t = np.asarray(times, float)
+    pos = np.array([[m.frame_pose_in_ground(f, {n: v[r] for n, v in coordinate_columns.items()})[0] for f in paths]
+                    for r in range(len(t))])
+    vel = np.gradient(pos, t, axis=0, edge_order=2)
+    return FrameReference(t, list(paths), np.gradient(vel, t, axis=0, edge_order=2))
+
+
+def double_pendulum_acceleration_tracking(reference: FrameReference = None, num_mesh_intervals: int = 20,
+                                          scheme: str = "hermite-simpson", fd_scheme: str = "central",
+                                          dynamics: str = "explicit") -> MocoStudy:
+    """testMocoGoals.cpp:327-361: the effort problem with the effort goal's
+    weight 0.001 and a MocoAccelerationTrackingGoal "tracking" on the frames
+    /bodyset/b0 and /bodyset/b1.  ``reference``: the two frames' linear
+    accelerations (the test: the effort solution's, HipNLP.
+    frame_accelerations); None: those of double_pendulum_swing_states by
+    accelerations_from_coordinates."""
+    st = double_pendulum_effort(num_mesh_intervals, scheme, effort_weight=0.001)
+    st.solver.optim_finite_difference_scheme = fd_scheme
+    st.solver.multibody_dynamics_mode = dynamics
+    m = st.problem.model
+    paths = ["/bodyset/b0", "/bodyset/b1"]
+    if reference is None:
+        sw = double_pendulum_swing_states()
+        reference = accelerations_from_coordinates(m, paths, sw.times, {
+            "q0": sw.columns["/jointset/j0/q0/value"], "q1": sw.columns["/jointset/j1/q1/value"]})
+    g = MocoAccelerationTrackingGoal("tracking", 1.0, reference=reference, frame_paths=paths)
+    m.add_table(g.reference_table(m))
+    st.problem.add_goal(g)
+    return st
+
+
+GAIT_ACCELERATION_FRAMES = ("/bodyset/pelvis", "/bodyset/tibia_r", "/bodyset/torso/imu_torso")
+
+
+def gait10dof18musc_accel_track(num_mesh_intervals: int = 200, dynamics: str = "explicit",
+                                frames=GAIT_ACCELERATION_FRAMES, **kw) -> MocoStudy:
+    """gait10dof18musc's study (``dynamics``: explicit or implicit multibody
+    dynamics) with a MocoAccelerationTrackingGoal "acceleration_tracking"
+    (weight 0.01; the torso sensor weighted 2) before its effort goal: the
+    accelerometer half of an inertial-sensor set on the pelvis, the right
+    tibia and an offset frame "imu_torso" on the torso at (-0.05, 0.3, 0.02).
+    The reference: accelerations_from_coordinates at the bundled walking
+    data's rows."""
+    st = gait10dof18musc(num_mesh_intervals, dynamics=dynamics, **kw)
+    m = st.problem.model
+    m.add_offset_frame("imu_torso", "torso", (-0.05, 0.3, 0.02), (0.2, -0.1, 0.4))
+    data = _load("walk_gait1018_state_reference.json")
+    bypath = {c.path + "/value": c.name for c in m.coordinates()}
+    cols = {bypath[k]: np.asarray(v, float) for k, v in data["columns"].items() if k in bypath}
+    imu = "/bodyset/torso/imu_torso"
+    g = MocoAccelerationTrackingGoal("acceleration_tracking", 0.01,
+                                     reference=accelerations_from_coordinates(m, frames, data["time"], cols),
+                                     frame_weights={imu: 2.0} if imu in frames else {})
+    m.add_table(g.reference_table(m))
+    st.problem.goals.insert(len(st.problem.goals) - 1, g)   # before the effort goal
+    return st
+
+
+def gait10dof18musc_accel_track_few(num_mesh_intervals: int = 3, **kw) -> MocoStudy:
+    """N = 3: gait10dof18musc_accel_track, for tests."""
+    return gait10dof18musc_accel_track(num_mesh_intervals, **kw)

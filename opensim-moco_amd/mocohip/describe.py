@@ -16,7 +16,7 @@ import numpy as np
 from .model import CoordinateActuator, DataTable, DeGrooteFregly2016Muscle
 from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm, MocoControlBoundConstraint,
                       MocoControlGoal, MocoFinalTimeGoal, MocoFrameDistanceConstraint, MocoInitialActivationGoal,
-                      MocoAngularVelocityTrackingGoal, MocoJointReactionGoal,
+                      MocoAccelerationTrackingGoal, MocoAngularVelocityTrackingGoal, MocoJointReactionGoal,
                       MocoMarkerFinalGoal, MocoMarkerTrackingGoal, MocoOrientationTrackingGoal,
                       MocoTranslationTrackingGoal,
                       MocoStateTrackingGoal, MocoSumSquaredStateGoal, PiecewiseLinearFunction)
@@ -175,12 +175,13 @@ def describe(study) -> str:
                                  str(int(bool(g.allow_unused_references))), str(len(ref.labels))]
                                 + [f"{_s(k)} {_d(v)}" for k, v in zip(ref.labels, ref.weights())]))
         elif isinstance(g, (MocoTranslationTrackingGoal, MocoOrientationTrackingGoal,
-                            MocoAngularVelocityTrackingGoal)):
+                            MocoAngularVelocityTrackingGoal, MocoAccelerationTrackingGoal)):
             # the tracked frames (frame_paths applied to the reference's
             # labels) with their weights; the flattened table is one of the
             # model's
             kind = ("translation_tracking" if isinstance(g, MocoTranslationTrackingGoal) else
                     "orientation_tracking" if isinstance(g, MocoOrientationTrackingGoal) else
+                    "acceleration_tracking" if isinstance(g, MocoAccelerationTrackingGoal) else
                     "angular_velocity_tracking")
             paths = g.tracked_frame_paths()
             out.append(" ".join(["goal", kind, _s(g.name), _d(g.weight), _s(g.reference_name()), str(len(paths))]

@@ -392,6 +392,32 @@ class MocoAngularVelocityTrackingGoal(_FrameTrackingGoal):
 
 
 @dataclass
+class MocoAccelerationTrackingGoal(_FrameTrackingGoal):
+    """MocoAccelerationTrackingGoal (Moco/Moco/MocoGoal/
+    MocoAccelerationTrackingGoal.{h,cpp}): the integral over the phase of
+    sum_f w_f |linear acceleration of the origin of model frame f in ground -
+    reference_f(t)|^2, times the weight (include/mocohip.h
+    MH_GOAL_ACCELERATION_TRACKING).  ``reference`` holds Vec3 columns
+    (``values[row][frame][xyz]``, expressed in ground; the kinematic
+    acceleration, without gravity).  There is no ``states_reference``: the
+    reference class has no such property (states do not determine
+    accelerations), and one is refused."""
+    name: str = "acceleration_tracking"
+    WHAT = "acceleration"
+    SUFFIXES = ("acceleration_x", "acceleration_y", "acceleration_z")
+
+    def tracked_frame_paths(self) -> List[str]:
+        if self.states_reference is not None:
+            raise ValueError("MocoAccelerationTrackingGoal: a states reference cannot be given (the goal has an "
+                             "acceleration reference only: states do not determine accelerations)")
+        return super().tracked_frame_paths()
+
+    @staticmethod
+    def _flatten(v):
+        return np.asarray(v, float).reshape(len(v), 3)
+
+
+@dataclass
 class MocoJointReactionGoal:
     """MocoJointReactionGoal (Moco/Moco/MocoGoal/MocoJointReactionGoal.{h,cpp}):
     the integral over the phase of the weighted sum of squares of the chosen
@@ -792,6 +818,14 @@ class ProblemRep:
                     raise NotImplementedError(f"{type(g).__name__} with prescribed kinematics "
                                               "(the coordinates are not NLP states)")
                 self._frame_tracking_terms(model, g, gs, gidx, gcol, gw)
+            elif isinstance(g, MocoAccelerationTrackingGoal):
+                if kin is not None:
+                    raise NotImplementedError("MocoAccelerationTrackingGoal with prescribed kinematics "
+                                              "(the accelerations are not the NLP's)")
+                if problem.parameters:
+                    raise NotImplementedError("MocoAccelerationTrackingGoal with MocoParameters "
+                                              "(the goals' gradient along a parameter is defined as 0)")
+                self._frame_tracking_terms(model, g, gs, gidx, gcol, gw)
             elif isinstance(g, MocoJointReactionGoal):
                 if kin is not None:
                     raise NotImplementedError("MocoJointReactionGoal with prescribed kinematics "
@@ -1086,14 +1120,17 @@ class ProblemRep:
     def _frame_tracking_terms(self, model: Model, g: "_FrameTrackingGoal", gs, gidx, gcol, gw):
         """MocoTranslationTrackingGoal / MocoOrientationTrackingGoal::
         initializeOnModelImpl: four terms per tracked frame (kind 9, as a
-        marker's; kind 12: the angular-velocity columns with zero weights,
-        then the weight) or ten (kind 10: R_BO, the quaternion columns, the
+        marker's; kind 15 the same with the acceleration columns; kind 12:
+        the angular-velocity columns with zero weights, then the weight) or
+        ten (kind 10: R_BO, the quaternion columns, the
         weight);
         include/mocohip.h."""
         orient = isinstance(g, MocoOrientationTrackingGoal)
         angvel = isinstance(g, MocoAngularVelocityTrackingGoal)
         gs.kind = (abi.MH_GOAL_ORIENTATION_TRACKING if orient else
-                   abi.MH_GOAL_ANGULAR_VELOCITY_TRACKING if angvel else abi.MH_GOAL_TRANSLATION_TRACKING)
+                   abi.MH_GOAL_ANGULAR_VELOCITY_TRACKING if angvel else
+                   abi.MH_GOAL_ACCELERATION_TRACKING if isinstance(g, MocoAccelerationTrackingGoal) else
+                   abi.MH_GOAL_TRANSLATION_TRACKING)
         paths = g.tracked_frame_paths()
         name = g.reference_name()
         if name not in self.compiled.table_index:

@@ -607,6 +607,37 @@ class HipNLP(_NLPBase):
         t = x[0] + (x[1] - x[0]) * grid
         return self.eval_joint_reaction(names.index(goal_name), np.column_stack([t, self.point_inputs(x)]))
 
+    def eval_frame_accelerations(self, goal: int, inputs: np.ndarray) -> np.ndarray:
+        """Rows [t, point inputs] (as eval_dae) -> [rows, frames, 3]: the
+        linear acceleration in ground of the origin of every frame that
+        acceleration-tracking goal ``goal`` (its index among the problem's
+        goals) tracks (mh_eval_frame_accelerations)."""
+        inputs = np.ascontiguousarray(inputs, float)
+        npts = inputs.shape[0]
+        assert inputs.shape[1] == 1 + self.NI
+        # (a goal the library refuses -- out of range, another kind -- gets a one-frame buffer)
+        known = 0 <= int(goal) < len(self.rep.goal_names)
+        nf = int(self.rep._goals[int(goal)].term_count) // 4 if known else 0
+        out = np.empty((npts, max(nf, 1), 3))
+        self._check(self._fn("eval_frame_accelerations")(self.ctx, int(goal), npts, abi.dptr(inputs),
+                                                         abi.dptr(out)))
+        return out[:, :nf]
+
+    def frame_accelerations(self, trajectory, goal_name: str) -> np.ndarray:
+        """[grid points, frames, 3]: the linear accelerations in ground of the
+        frames of the MocoAccelerationTrackingGoal named ``goal_name`` at
+        every grid point of ``trajectory`` (a MocoTrajectory on this NLP's
+        grid, or an iterate x) -- what the reference gets from
+        analyze(model, solution, {"<frame>|linear_acceleration"})."""
+        names = list(self.rep.goal_names)
+        if goal_name not in names:
+            raise ValueError(f"no goal '{goal_name}' in the problem")
+        x = trajectory.to_iterate(self) if hasattr(trajectory, "to_iterate") else np.asarray(trajectory, float)
+        from .trajectory import nlp_grid
+        grid = nlp_grid(self)
+        t = x[0] + (x[1] - x[0]) * grid
+        return self.eval_frame_accelerations(names.index(goal_name), np.column_stack([t, self.point_inputs(x)]))
+
     def eval_g(self, x, new_x=True):
         x = np.ascontiguousarray(x, float)
         g = np.empty(max(self.row_end - self.row_begin, 1))
