@@ -568,7 +568,124 @@ enum mh_goal_kind {
      * acceleration variable; every other entry keeps its bits.  Goals of this
      * kind on one problem share the evaluations.  mh_batch_* accepts contexts
      * with such goals and never reads them, as for every other goal. */
-    MH_GOAL_ACCELERATION_TRACKING = 15
+    MH_GOAL_ACCELERATION_TRACKING = 15,
+    /* MocoOutputGoal (MocoOutputGoal.cpp:29-60) over one output of a
+     * DeGrooteFregly2016Muscle (16 stays unassigned):
+     *     weight * duration * quadrature over every grid point of
+     *         L = value of the output (it may be negative) / divisor
+     * Exactly one term: goal_index = the muscle, goal_column = the output
+     * (enum mh_muscle_output), goal_weight = the divisor: 1.0, or the model's
+     * total mass for divide_by_mass (positive and finite).  mh_goal.exponent
+     * and mh_goal.table are unused.  divide_by_displacement is not available
+     * (it needs calcSystemDisplacement; a follow-up).
+     * A velocity-stage goal: the value reads the time, the coordinates, the
+     * speeds and the muscle's own activation / excitation, normalized tendon
+     * force and tendon-force derivative variable, and nothing of the dynamics
+     * (no accelerations, mass matrix or joint loads), so it is accepted with
+     * explicit and implicit multibody dynamics, rigid, explicit and implicit
+     * compliant tendons, couplers, and with prescribed kinematics (q and u from
+     * the kinematics table at the lane's time).  Not with MocoParameters
+     * (MH_ERR_UNSUPPORTED, as kinds 14 and 15: the goals' gradient along a
+     * parameter is defined as 0).
+     * Per lane: the poses and spatial velocities of the bodies that carry the
+     * muscle's path points and wrap surfaces, and of their ancestors, by the
+     * statements of the DAE's forward pass (position and velocity parts); the
+     * muscle's current path (conditional and moving points, wrapping) with its
+     * length and lengthening speed as the DAE forms them; then the output.
+     * Gradient: finite-difference quotients of L with k_grad's formulas, added
+     * to the entries the other goals wrote, over t0, tf and only those point
+     * inputs the value can read: the coordinate values and speeds (none with
+     * prescribed kinematics, where only t0 and tf move q and u), the muscle's
+     * activation state (its excitation control when it has no activation
+     * dynamics), its normalized-tendon-force state and its tendon-force
+     * derivative variable.  Every other entry keeps its bits.  Goals of this
+     * kind on one problem share one launch.  mh_batch_* accepts contexts with
+     * such goals and never reads them, as for every other goal. */
+    MH_GOAL_OUTPUT = 17
+};
+/* The outputs of a DeGrooteFregly2016Muscle that MH_GOAL_OUTPUT integrates and
+ * mh_eval_muscle_outputs reads.  Ids 0 and 1 are its GeometryPath's outputs
+ * (<muscle>/geometrypath|length, |lengthening_speed); 26-29 are declared in
+ * DeGrooteFregly2016Muscle.h:117-124; the names of 2-25 and 30-33 are
+ * opensim-core's Muscle outputs, whose source is not part of the reference
+ * tree: where the reference's examples spell one (normalized_fiber_length,
+ * passive_force_multiplier: exampleSquatToStand.m) that spelling is used,
+ * otherwise this list is the definition.  With LMT / VMT the path's length and
+ * lengthening speed, a = the activation state (the excitation when activation
+ * dynamics are ignored), ftn = the normalized-tendon-force state and dft the
+ * tendon-force derivative variable (implicit tendon dynamics), the values are
+ * those of calcMuscleLengthInfoHelper (DeGrooteFregly2016Muscle.cpp:240-275),
+ * calcFiberVelocityInfoHelper (277-323), calcMuscleDynamicsInfoHelper
+ * (325-415) and the getters at 803-824, every operation rounded on its own (no
+ * fused multiply-add; the curves are the DAE's own functions), in the DAE's
+ * expressions: tendon_force is the tension the DAE applies and
+ * lengthening_speed the speed it uses, to rounding (the DAE's own evaluation
+ * is compiled with the compiler's default contraction, so its last bits may
+ * differ from the values here; the tests hold m udot = m g - tendon_force to
+ * 1e-10):
+ *   tendon:   nTL = 1 (rigid) or the inverse tendon curve of ftn;
+ *             tendon_strain = nTL - 1;  tendon_length = slack * nTL
+ *   fibre:    fiber_length_along_tendon = LMT - tendon_length
+ *             fiber_length = sqrt(along^2 + width^2);  normalized = / optimal
+ *             cos_pennation_angle = along / fiber_length
+ *             pennation_angle = asin(width / fiber_length)
+ *             active_force_length_multiplier, passive_force_multiplier: the
+ *             curves at the normalized length (passive: 0 when ignored)
+ *   velocity: explicit compliant tendon: force_velocity_multiplier =
+ *             (ftn / cos - fPE) / (a fAL), normalized_fiber_velocity its inverse
+ *             curve, fiber_velocity = that * vmax, along tendon = / cos,
+ *             tendon_velocity = VMT - along;  otherwise tendon_velocity = slack
+ *             * (0, or dft over the tendon curve's derivative), along = VMT -
+ *             tendon_velocity, fiber_velocity = along * cos, normalized = /
+ *             vmax, multiplier = the curve;  pennation_angular_velocity =
+ *             -fiber_velocity / fiber_length * (width / along)
+ *   force:    active_fiber_force = Fmax (a fAL fV);  elastic = Fmax fPE;
+ *             damping = Fmax * fiber_damping * normalized velocity;
+ *             passive_fiber_force = elastic + damping;  fiber_force = active +
+ *             elastic + damping;  tendon_force = fiber_force * cos (rigid) or
+ *             Fmax ftn;  every "_along_tendon" = the value * cos
+ *   power:    fiber_active_power = -(active + damping) * fiber_velocity
+ *             fiber_passive_power = -elastic * fiber_velocity
+ *             tendon_power = -tendon_force * tendon_velocity
+ *             muscle_power = -tendon_force * VMT
+ * Stiffness and potential-energy outputs need curve derivatives the device
+ * does not have: a follow-up. */
+enum mh_muscle_output {
+    MH_MO_LENGTH = 0,
+    MH_MO_LENGTHENING_SPEED = 1,
+    MH_MO_ACTIVATION = 2,
+    MH_MO_EXCITATION = 3,
+    MH_MO_FIBER_LENGTH = 4,
+    MH_MO_NORMALIZED_FIBER_LENGTH = 5,
+    MH_MO_PENNATION_ANGLE = 6,
+    MH_MO_COS_PENNATION_ANGLE = 7,
+    MH_MO_TENDON_LENGTH = 8,
+    MH_MO_TENDON_STRAIN = 9,
+    MH_MO_FIBER_LENGTH_ALONG_TENDON = 10,
+    MH_MO_ACTIVE_FORCE_LENGTH_MULTIPLIER = 11,
+    MH_MO_PASSIVE_FORCE_MULTIPLIER = 12,
+    MH_MO_FIBER_VELOCITY = 13,
+    MH_MO_NORMALIZED_FIBER_VELOCITY = 14,
+    MH_MO_FIBER_VELOCITY_ALONG_TENDON = 15,
+    MH_MO_TENDON_VELOCITY = 16,
+    MH_MO_FORCE_VELOCITY_MULTIPLIER = 17,
+    MH_MO_PENNATION_ANGULAR_VELOCITY = 18,
+    MH_MO_FIBER_FORCE = 19,
+    MH_MO_FIBER_FORCE_ALONG_TENDON = 20,
+    MH_MO_ACTIVE_FIBER_FORCE = 21,
+    MH_MO_PASSIVE_FIBER_FORCE = 22,
+    MH_MO_ACTIVE_FIBER_FORCE_ALONG_TENDON = 23,
+    MH_MO_PASSIVE_FIBER_FORCE_ALONG_TENDON = 24,
+    MH_MO_TENDON_FORCE = 25,
+    MH_MO_PASSIVE_FIBER_ELASTIC_FORCE = 26,
+    MH_MO_PASSIVE_FIBER_ELASTIC_FORCE_ALONG_TENDON = 27,
+    MH_MO_PASSIVE_FIBER_DAMPING_FORCE = 28,
+    MH_MO_PASSIVE_FIBER_DAMPING_FORCE_ALONG_TENDON = 29,
+    MH_MO_FIBER_ACTIVE_POWER = 30,
+    MH_MO_FIBER_PASSIVE_POWER = 31,
+    MH_MO_TENDON_POWER = 32,
+    MH_MO_MUSCLE_POWER = 33,
+    MH_MO_COUNT = 34
 };
 typedef struct mh_goal {
     int32_t kind;
@@ -1013,6 +1130,15 @@ int mh_eval_joint_reaction(mh_ctx* ctx, int32_t goal, int32_t npoints, const dou
  * row).  npoints <= 0: MH_ERR_INVALID.  Synchronous. */
 int mh_eval_frame_accelerations(mh_ctx* ctx, int32_t goal, int32_t npoints, const double* inputs,
         double* out);
+/* Muscle outputs at npoints rows [time, NI point inputs] (as for mh_eval_dae):
+ * out[row][k] = output output[k] (enum mh_muscle_output) of muscle muscle[k],
+ * k < nout, the value MH_GOAL_OUTPUT integrates (before its divisor).  Not tied
+ * to a goal: any context serves.  With prescribed kinematics q and u are the
+ * kinematics table's at the row's time.  npoints <= 0, nout <= 0, a muscle or
+ * an output out of range: MH_ERR_INVALID; a problem with MocoParameters:
+ * MH_ERR_UNSUPPORTED.  Synchronous. */
+int mh_eval_muscle_outputs(mh_ctx* ctx, int32_t nout, const int32_t* muscle, const int32_t* output,
+        int32_t npoints, const double* inputs, double* out);
 /* Path-constraint probe, the counterpart of mh_eval_dae for the path
  * callback: the npath path-equation values of npoints probe rows [time, point
  * inputs (NS + NC + NDV + ...)] (the row of mh_get_callback_sparsity, W

@@ -36,6 +36,7 @@
 #include <OpenSim/Moco/MocoGoal/MocoAngularVelocityTrackingGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoJointReactionGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoOrientationTrackingGoal.h>
+#include <OpenSim/Moco/MocoGoal/MocoOutputGoal.h>
 #include <OpenSim/Moco/MocoGoal/MocoTranslationTrackingGoal.h>
 #include <OpenSim/Simulation/StatesTrajectory.h>
 #include <OpenSim/Moco/MocoGoal/MocoStateTrackingGoal.h>
@@ -698,6 +699,34 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
                 }
                 prob.model.add_offset_frame(of);
             }
+        } else if (dynamic_cast<const MocoOutputGoal*>(&g)) {
+            // an output of a DeGrooteFregly2016Muscle (include/mocohip.h enum
+            // mh_muscle_output; <muscle path>|<output>, or its GeometryPath's
+            // length / lengthening_speed): the component and the output's name
+            // are checked here.  divide_by_displacement needs
+            // calcSystemDisplacement.
+            hg.kind = mhb::Goal::OUTPUT;
+            hg.output_path = g.getPropertyByName("output_path").getValue<std::string>();
+            hg.divide_by_mass = g.getPropertyByName("divide_by_mass").getValue<bool>();
+            hg.divide_by_displacement = g.getPropertyByName("divide_by_displacement").getValue<bool>();
+            OPENSIM_THROW_IF(hg.divide_by_displacement, Exception,
+                    "MocoHipSolver: goal '{}': MocoOutputGoal with divide_by_displacement is not supported",
+                    g.getName());
+            OPENSIM_THROW_IF(hg.output_path.empty(), Exception, "No output_path provided.");
+            std::string comp = hg.output_path.substr(0, hg.output_path.find('|'));
+            const std::string gp = "/geometrypath";
+            if (comp.size() >= gp.size() && comp.compare(comp.size() - gp.size(), gp.size(), gp) == 0)
+                comp.resize(comp.size() - gp.size());
+            OPENSIM_THROW_IF(!model.hasComponent<DeGrooteFregly2016Muscle>(comp), Exception,
+                    "MocoHipSolver: goal '{}': output '{}' is not an output of a DeGrooteFregly2016Muscle; only "
+                    "those are supported (include/mocohip.h enum mh_muscle_output)",
+                    g.getName(), hg.output_path);
+            const size_t bar = hg.output_path.find('|');
+            OPENSIM_THROW_IF(bar == std::string::npos || mhb::muscle_output_id(hg.output_path.substr(bar + 1)) < 0,
+                    Exception,
+                    "MocoHipSolver: goal '{}': output '{}' is not a supported output of a DeGrooteFregly2016Muscle "
+                    "(include/mocohip.h enum mh_muscle_output)",
+                    g.getName(), hg.output_path);
         } else {
             OPENSIM_THROW(Exception, "MocoHipSolver: goal '{}' of type '{}' is not supported (SURVEY §8 A11)",
                     g.getName(), g.getConcreteClassName());

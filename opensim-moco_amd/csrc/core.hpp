@@ -2209,7 +2209,8 @@ __host__ __device__ __forceinline__ bool goal_tracked_items(int kind) {
 // joint-reaction goal (kind 14) is an integral goal: goal_integrand gives 0.0
 // for it, and k_joint_reaction / k_joint_reaction_grad write its slot and add
 // its gradient after k_integrand / k_grad.  The acceleration-tracking goal
-// (kind 15) likewise, by k_accel_tracking / k_accel_tracking_grad.
+// (kind 15) likewise, by k_accel_tracking / k_accel_tracking_grad, and the
+// muscle-output goal (kind 17) by k_muscle_outputs / k_muscle_outputs_grad.
 __host__ __device__ __forceinline__ bool goal_integral(int kind) {
     return kind != MH_GOAL_FINAL_TIME && kind != MH_GOAL_MARKER_FINAL && !goal_tracked_items(kind);
 }
@@ -2601,6 +2602,12 @@ struct mh_ctx {
     Lanes lanes_at{};
     double* d_at = nullptr;
     const int* d_at_live = nullptr;
+    // muscle-output goals (kind 17): their count, the lanes of
+    // k_muscle_outputs in gradient mode (ND = NI - NSL + 2) and its lane
+    // values [G][stride][nmo]
+    int nmo = 0;
+    Lanes lanes_mo{};
+    double* d_mo = nullptr;
     bool use_roles = false;        // MOCOHIP_ROLES=1: k_role (+ k_couple) for the Jacobian lanes
     int role_threads = 256;        // k_role workgroup size (MOCOHIP_ROLE_THREADS: 64..512)
     int iv_threads = 1024;         // k_interval workgroup size, Jacobian lanes (MOCOHIP_IV_THREADS: 256..1024)
@@ -3086,6 +3093,15 @@ struct AccelTrackingBackend {
     void (*probe)(mh_ctx*, int goal, int np, const double* in, double* out);
 };
 const AccelTrackingBackend* accel_tracking_backends();
+// The muscle-output goals' kernels (muscle_outputs.hip), selected and kept
+// apart in the same way.  eval: the goals' integrands (mode 0) or integrands
+// and gradient parts (mode 1); probe: mh_eval_muscle_outputs' rows (mus /
+// which: device arrays of nout muscles and outputs).
+struct MuscleOutputsBackend {
+    void (*eval)(mh_ctx*, const double* x, int mode);
+    void (*probe)(mh_ctx*, int nout, const int* mus, const int* which, int np, const double* in, double* out);
+};
+const MuscleOutputsBackend* muscle_outputs_backends();
 // A model-specialized back end (generated/gen_<model>.hip): the task kernels
 // (default) and the one-lane-per-DAE kernel (MOCOHIP_BACKEND=lane), for the
 // model structure match() accepts (multibody dynamics mode and prescribed

@@ -356,6 +356,97 @@ __device__ __forceinline__ void dgf_eval(const DevModel& M, int im, double LMT, 
     (void)fiberWidth;
 }
 
+// One output of a muscle (include/mocohip.h mh_muscle_output `which`) from
+// its muscle-tendon length and lengthening speed and its own inputs:
+// calcMuscleLengthInfoHelper, calcFiberVelocityInfoHelper and
+// calcMuscleDynamicsInfoHelper (DeGrooteFregly2016Muscle.cpp:240-415) in
+// dgf_eval's expressions (tendon_force is its T to rounding: dgf_eval is
+// compiled with the default contraction), each operation rounded on its own.
+// Not used by the DAE.
+__device__ __forceinline__ double dgf_output(const DevModel& M, int im, int which, double LMT, double VMT,
+        double act, double exc, double ftn, bool compliant, bool implicit_tendon, double dft) {
+#pragma clang fp contract(off)
+    const mh_muscle& mu = M.mus[im];
+    const double* dv = M.mus_derived + (long)im * MUS_DERIVED;
+    const double fiberWidth = dv[0], sqW = dv[1], vmax = dv[2], kT = dv[3];
+    const double peOffset = dv[4], peDenom = dv[5];
+    const double lopt = mu.optimal_fiber_length, lts = mu.tendon_slack_length;
+    double normTendonLength = 1.0;
+    if (compliant) normTendonLength = log((1.0 / DGF_c1) * (ftn + DGF_c3)) / kT + DGF_c2;
+    const double tendonStrain = normTendonLength - 1.0;
+    const double tendonLength = lts * normTendonLength;
+    const double flat = LMT - tendonLength;
+    const double fiberLength = sqrt(flat * flat + sqW);
+    const double nfl = fiberLength / lopt;
+    const double cosPenn = flat / fiberLength;
+    double fPE = 0.0;
+    if (!mu.ignore_passive_fiber_force) {
+        const double e0 = mu.passive_fiber_strain_at_one_norm_force;
+        fPE = (exp(4.0 * (nfl - 1.0) / e0) - peOffset) / peDenom;
+    }
+    const double fAL = dgf_fal(mu.active_force_width_scale, nfl);
+    double nfv, fV, fiberVelocity, fvat, tendonVelocity;
+    if (compliant && !implicit_tendon) {
+        const double nff = ftn / cosPenn;
+        fV = (nff - fPE) / (act * fAL);
+        nfv = dgf_fv_inv(fV);
+        fiberVelocity = nfv * vmax;
+        fvat = fiberVelocity / cosPenn;
+        tendonVelocity = VMT - fvat;
+    } else {
+        const double ntv = compliant ? dft / (DGF_c1 * kT * exp(kT * (normTendonLength - DGF_c2))) : 0.0;
+        tendonVelocity = lts * ntv;
+        fvat = VMT - tendonVelocity;
+        fiberVelocity = fvat * cosPenn;
+        nfv = fiberVelocity / vmax;
+        fV = dgf_fv(nfv);
+    }
+    const double Fmax = mu.max_isometric_force;
+    const double activeF = Fmax * (act * fAL * fV);
+    const double conPass = Fmax * fPE;
+    const double nonCon = Fmax * mu.fiber_damping * nfv;
+    const double total = activeF + conPass + nonCon;
+    const double passiveF = conPass + nonCon;
+    const double T = compliant ? Fmax * ftn : total * cosPenn;
+    switch (which) {
+    case MH_MO_LENGTH: return LMT;
+    case MH_MO_LENGTHENING_SPEED: return VMT;
+    case MH_MO_ACTIVATION: return act;
+    case MH_MO_EXCITATION: return exc;
+    case MH_MO_FIBER_LENGTH: return fiberLength;
+    case MH_MO_NORMALIZED_FIBER_LENGTH: return nfl;
+    case MH_MO_PENNATION_ANGLE: return asin(fiberWidth / fiberLength);
+    case MH_MO_COS_PENNATION_ANGLE: return cosPenn;
+    case MH_MO_TENDON_LENGTH: return tendonLength;
+    case MH_MO_TENDON_STRAIN: return tendonStrain;
+    case MH_MO_FIBER_LENGTH_ALONG_TENDON: return flat;
+    case MH_MO_ACTIVE_FORCE_LENGTH_MULTIPLIER: return fAL;
+    case MH_MO_PASSIVE_FORCE_MULTIPLIER: return fPE;
+    case MH_MO_FIBER_VELOCITY: return fiberVelocity;
+    case MH_MO_NORMALIZED_FIBER_VELOCITY: return nfv;
+    case MH_MO_FIBER_VELOCITY_ALONG_TENDON: return fvat;
+    case MH_MO_TENDON_VELOCITY: return tendonVelocity;
+    case MH_MO_FORCE_VELOCITY_MULTIPLIER: return fV;
+    case MH_MO_PENNATION_ANGULAR_VELOCITY: return -fiberVelocity / fiberLength * (fiberWidth / flat);
+    case MH_MO_FIBER_FORCE: return total;
+    case MH_MO_FIBER_FORCE_ALONG_TENDON: return total * cosPenn;
+    case MH_MO_ACTIVE_FIBER_FORCE: return activeF;
+    case MH_MO_PASSIVE_FIBER_FORCE: return passiveF;
+    case MH_MO_ACTIVE_FIBER_FORCE_ALONG_TENDON: return activeF * cosPenn;
+    case MH_MO_PASSIVE_FIBER_FORCE_ALONG_TENDON: return passiveF * cosPenn;
+    case MH_MO_TENDON_FORCE: return T;
+    case MH_MO_PASSIVE_FIBER_ELASTIC_FORCE: return conPass;
+    case MH_MO_PASSIVE_FIBER_ELASTIC_FORCE_ALONG_TENDON: return conPass * cosPenn;
+    case MH_MO_PASSIVE_FIBER_DAMPING_FORCE: return nonCon;
+    case MH_MO_PASSIVE_FIBER_DAMPING_FORCE_ALONG_TENDON: return nonCon * cosPenn;
+    case MH_MO_FIBER_ACTIVE_POWER: return -(activeF + nonCon) * fiberVelocity;
+    case MH_MO_FIBER_PASSIVE_POWER: return -conPass * fiberVelocity;
+    case MH_MO_TENDON_POWER: return -T * tendonVelocity;
+    case MH_MO_MUSCLE_POWER: return -T * VMT;
+    default: return 0.0;
+    }
+}
+
 // ---- muscle wrapping over cylinders -------------------------------------
 // The oracle's wrap_cylinder / wrap_segment / apply_wraps (oracle/oracle.c:
 // GeometryPath::applyWrapObjects, WrapObject::wrapPathSegment,

@@ -688,6 +688,22 @@ static void parameter_targets(const Problem& P, const CompiledModel& C, ProblemR
     }
 }
 
+int muscle_output_id(const std::string& name) {
+    static const char* const outputs[MH_MO_COUNT] = {
+        "length", "lengthening_speed", "activation", "excitation", "fiber_length", "normalized_fiber_length",
+        "pennation_angle", "cos_pennation_angle", "tendon_length", "tendon_strain", "fiber_length_along_tendon",
+        "active_force_length_multiplier", "passive_force_multiplier", "fiber_velocity", "normalized_fiber_velocity",
+        "fiber_velocity_along_tendon", "tendon_velocity", "force_velocity_multiplier", "pennation_angular_velocity",
+        "fiber_force", "fiber_force_along_tendon", "active_fiber_force", "passive_fiber_force",
+        "active_fiber_force_along_tendon", "passive_fiber_force_along_tendon", "tendon_force",
+        "passive_fiber_elastic_force", "passive_fiber_elastic_force_along_tendon", "passive_fiber_damping_force",
+        "passive_fiber_damping_force_along_tendon", "fiber_active_power", "fiber_passive_power", "tendon_power",
+        "muscle_power"};
+    for (int k = 0; k < (int)MH_MO_COUNT; ++k)
+        if (name == outputs[k]) return k;
+    return -1;
+}
+
 void make_rep(const Problem& P, ProblemRep& R) {
     R = ProblemRep();
     const Model& model = P.model;
@@ -997,6 +1013,45 @@ void make_rep(const Problem& P, ProblemRep& R) {
             for (int k = 0; k < 9; ++k) term(b, e, R_EO[k]);
             for (int i = 0; i < 6; ++i) term(b, -1, w6[i]);
             term(b, child ? 1 : 0, den);
+            break;
+        }
+        case Goal::OUTPUT: {
+            // MocoOutputGoal::initializeOnModelImpl (problem.py MocoOutputGoal,
+            // parse_muscle_output_path): one term -- the muscle, the output
+            // (enum mh_muscle_output), the divisor (Model::getTotalMass)
+            if (g.output_path.empty()) fail("No output_path provided.");
+            if (g.divide_by_displacement)
+                fail("MocoOutputGoal with divide_by_displacement (calcSystemDisplacement is not available)");
+            if (!P.parameters.empty())
+                fail("MocoOutputGoal with MocoParameters (the goals' gradient along a parameter is defined as 0)");
+            const std::string supported = "supported: the outputs of a DeGrooteFregly2016Muscle listed in "
+                                          "include/mocohip.h (enum mh_muscle_output), as <muscle path>|<output>; "
+                                          "length and lengthening_speed also as <muscle path>/geometrypath|...";
+            const size_t bar = g.output_path.find('|');
+            if (bar == std::string::npos || bar + 1 >= g.output_path.size())
+                fail("output path '" + g.output_path + "' is not of the form <component path>|<output>; " + supported);
+            std::string comp = g.output_path.substr(0, bar);
+            const std::string out = g.output_path.substr(bar + 1);
+            const std::string gp = "/geometrypath";
+            const bool path_output = comp.size() >= gp.size() && comp.compare(comp.size() - gp.size(), gp.size(), gp) == 0;
+            if (path_output) comp.resize(comp.size() - gp.size());
+            int im = -1;
+            for (size_t i = 0; i < model.muscles.size() && im < 0; ++i)
+                if (comp == model.muscles[i].path || comp == model.muscles[i].name) im = (int)i;
+            if (im < 0)
+                fail("output path '" + g.output_path + "': component '" + comp + "' is not a DeGrooteFregly2016Muscle "
+                     "of the model; " + supported);
+            int which = -1;
+            const int id = muscle_output_id(out);
+            if (id >= 0 && (!path_output || id < 2)) which = id;
+            if (which < 0) fail("output path '" + g.output_path + "': no supported output '" + out + "'; " + supported);
+            double den = 1.0;
+            if (g.divide_by_mass) {
+                den = 0.0;
+                for (auto& body : model.bodies) den += body.mass;
+            }
+            gs.kind = MH_GOAL_OUTPUT;
+            term(im, which, den);
             break;
         }
         case Goal::AUX_DERIVATIVES: {
@@ -1528,6 +1583,11 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
                 const long nm = t.i();
                 for (long k = 0; k < nm; ++k) g.reaction_measures.push_back(t.s());
                 g.weights = read_weights(t);
+            } else if (kind == "output") {
+                g.kind = Goal::OUTPUT;
+                g.name = t.s(); g.weight = t.d(); g.output_path = t.s();
+                g.divide_by_mass = t.i() != 0;
+                g.divide_by_displacement = t.i() != 0;
             } else if (kind == "aux_derivatives") {
                 g.kind = Goal::AUX_DERIVATIVES;
                 g.name = t.s(); g.weight = t.d();

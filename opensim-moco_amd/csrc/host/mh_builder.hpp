@@ -248,7 +248,7 @@ struct VariableInfo {
 struct Goal {
     enum Kind { CONTROL, STATE_TRACKING, FINAL_TIME, SUM_SQUARED_STATE, INITIAL_ACTIVATION, MARKER_FINAL,
                 AUX_DERIVATIVES, MARKER_TRACKING, TRANSLATION_TRACKING, ORIENTATION_TRACKING,
-                ANGULAR_VELOCITY_TRACKING, JOINT_REACTION, ACCELERATION_TRACKING };
+                ANGULAR_VELOCITY_TRACKING, JOINT_REACTION, ACCELERATION_TRACKING, OUTPUT };
     Kind kind = CONTROL;
     std::string name;
     double weight = 1.0;
@@ -273,6 +273,9 @@ struct Goal {
     // (reaction_weights) are in `weights`
     std::string joint_path, loads_frame = "parent", expressed_in_frame_path;
     std::vector<std::string> reaction_measures;
+    // output goal (problem.py MocoOutputGoal)
+    std::string output_path;
+    bool divide_by_mass = false, divide_by_displacement = false;
 };
 
 // Bound function of MocoControlBoundConstraint: OpenSim::Constant,
@@ -366,6 +369,9 @@ struct ProblemRep {
 };
 
 // Throws std::runtime_error with the reference's message on invalid input.
+// The id of a DeGrooteFregly2016Muscle output by its name (include/mocohip.h
+// enum mh_muscle_output), -1 for a name that is not in the list.
+int muscle_output_id(const std::string& name);
 void make_rep(const Problem& p, ProblemRep& out);
 
 // MocoHipSolver settings (mocohip/solver.py) -> mh_options.

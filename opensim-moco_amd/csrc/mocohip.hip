@@ -1991,6 +1991,23 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
             }
             continue;
         }
+        if (G.kind == MH_GOAL_OUTPUT) {
+            // one term (include/mocohip.h): the muscle, the output, the divisor
+            if (G.term_begin < 0 || G.term_count != 1 || (int64_t)G.term_begin + G.term_count > p->nterms)
+                return set_err(MH_ERR_INVALID, "goal %d: output goal needs exactly one term", g);
+            if (p->nparameters > 0)
+                return set_err(MH_ERR_UNSUPPORTED, "goal %d: output goal with MocoParameters", g);
+            const int tb = G.term_begin, im = p->goal_index[tb], which = p->goal_column[tb];
+            if (im < 0 || im >= M.nmuscles)
+                return set_err(MH_ERR_INVALID, "goal %d: output goal: muscle %d out of range", g, im);
+            if (which < 0 || which >= MH_MO_COUNT)
+                return set_err(MH_ERR_INVALID, "goal %d: output goal: muscle output %d out of range", g, which);
+            const double den = p->goal_weight[tb];
+            if (!(den > 0.0) || !std::isfinite(den))
+                return set_err(MH_ERR_INVALID, "goal %d: output goal: divisor %g is not positive and finite", g,
+                               den);
+            continue;
+        }
         if (G.kind < MH_GOAL_CONTROL || (G.kind > MH_GOAL_MARKER_FINAL && !tracking))
             return set_err(MH_ERR_INVALID, "goal %d: unknown kind %d", g, G.kind);
         if (G.term_begin < 0 || G.term_count < 0 || (int64_t)G.term_begin + G.term_count > p->nterms ||
@@ -2577,6 +2594,12 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
         const std::vector<int> live = accel_tracking_live(c.get(), p);
         o_atlive = A.put(live.data(), live.size());
     }
+    // muscle-output goals: k_muscle_outputs' lanes and lane values (the same
+    // lanes as the joint-reaction goals')
+    c->nmo = 0;
+    for (const mh_goal& G : c->goals) c->nmo += G.kind == MH_GOAL_OUTPUT;
+    c->lanes_mo = c->lanes_jr;
+    const size_t o_mo = c->nmo ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_mo.stride * c->nmo) : 0;
     const size_t o_f = A.reserve(sizeof(double) * 4);
     const size_t o_epc = A.reserve(sizeof(double) * (size_t)std::max(1, c->ngoals));   // endpoint costs
     const int npts_iv = c->scheme == MH_HERMITE_SIMPSON ? 3 : 2;
@@ -2781,6 +2804,7 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
         c->d_at = (double*)(b + o_at);
         c->d_at_live = (const int*)(b + o_atlive);
     }
+    if (c->nmo) c->d_mo = (double*)(b + o_mo);
     c->has_marker = false;
     for (int g = 0; g < p->ngoals; ++g) c->has_marker |= p->goals[g].kind == MH_GOAL_MARKER_FINAL;
     if (MT.nm > 0) MT.tab = (const int*)(b + o_mttab);
@@ -3817,6 +3841,12 @@ static void launch_accel_tracking(mh_ctx* c, int mode) {
     accel_tracking_backends()[c->size_class].eval(c, c->d_x, mode);
 }
 
+// The muscle-output goals' likewise, after the acceleration-tracking goals'.
+static void launch_muscle_outputs(mh_ctx* c, int mode) {
+    if (c->nmo == 0) return;
+    muscle_outputs_backends()[c->size_class].eval(c, c->d_x, mode);
+}
+
 // The objective (partial = false) or this shard's partial of it (partial =
 // true: the integrals over the shard's own mesh intervals, d_quadp, and the
 // endpoint goals -- final time, final marker -- on the shard that owns the
@@ -3837,6 +3867,7 @@ static int eval_f_impl(mh_ctx* c, const double* x, double* f, bool partial) {
     launch_marker_tracking(c, L, 0);   // after k_integrand: the marker-tracking goals' slots
     launch_joint_reaction(c, 0);       // and the joint-reaction goals'
     launch_accel_tracking(c, 0);       // and the acceleration-tracking goals'
+    launch_muscle_outputs(c, 0);       // and the muscle-output goals'
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)
@@ -3872,6 +3903,7 @@ static int eval_grad_f_impl(mh_ctx* c, const double* x, double* grad, bool parti
     launch_marker_tracking(c, L, 1);   // after k_grad: adds to the coordinates' and the t0 / tf entries
     launch_joint_reaction(c, 1);       // after both: adds to every direction's entry
     launch_accel_tracking(c, 1);       // after the three: adds to its live directions' entries
+    launch_muscle_outputs(c, 1);       // after the four: adds to the entries of the inputs an output reads
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)   // after k_grad: adds to the final coordinates' entries
@@ -3911,6 +3943,7 @@ extern "C" int mh_eval_objective_terms(mh_ctx* c, const double* x, double* terms
     launch_marker_tracking(c, L, 0);
     launch_joint_reaction(c, 0);
     launch_accel_tracking(c, 0);
+    launch_muscle_outputs(c, 0);
     HIPCHK(hipGetLastError());
     if (c->has_marker)
         hipLaunchKernelGGL(k_marker_final, dim3((unsigned)c->ngoals), dim3(128), 0, c->stream, c->M, L, c->GS,
@@ -3991,6 +4024,38 @@ extern "C" int mh_eval_frame_accelerations(mh_ctx* c, int32_t goal, int32_t np, 
     HIPCHK(hipStreamSynchronize(c->stream));
     (void)hipFree(din);
     (void)hipFree(dout);
+    return MH_OK;
+}
+extern "C" int mh_eval_muscle_outputs(mh_ctx* c, int32_t nout, const int32_t* muscle, const int32_t* output,
+        int32_t np, const double* inputs, double* out) {
+    if (!c || !muscle || !output || !inputs || !out) return set_err(MH_ERR_INVALID, "bad argument");
+    if (np <= 0) return set_err(MH_ERR_INVALID, "mh_eval_muscle_outputs: %d rows", np);
+    if (nout <= 0) return set_err(MH_ERR_INVALID, "mh_eval_muscle_outputs: %d outputs", nout);
+    if (c->NPAR > 0) return set_err(MH_ERR_UNSUPPORTED, "mh_eval_muscle_outputs with MocoParameters");
+    for (int k = 0; k < nout; ++k) {
+        if (muscle[k] < 0 || muscle[k] >= c->M.nmus)
+            return set_err(MH_ERR_INVALID, "mh_eval_muscle_outputs: muscle %d out of range", muscle[k]);
+        if (output[k] < 0 || output[k] >= MH_MO_COUNT)
+            return set_err(MH_ERR_INVALID, "mh_eval_muscle_outputs: muscle output %d out of range", output[k]);
+    }
+    HIPCHK(hipSetDevice(c->device));
+    double *din = nullptr, *dout = nullptr;
+    int* dsel = nullptr;
+    const size_t nin = (size_t)np * (1 + c->NI), no = (size_t)np * nout;
+    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
+    HIPCHK(hipMalloc(&dout, sizeof(double) * no));
+    HIPCHK(hipMalloc(&dsel, sizeof(int) * 2 * (size_t)nout));
+    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dsel, muscle, sizeof(int) * nout, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dsel + nout, output, sizeof(int) * nout, hipMemcpyHostToDevice, c->stream));
+    (void)hipGetLastError();
+    muscle_outputs_backends()[c->size_class].probe(c, nout, dsel, dsel + nout, np, din, dout);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * no, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    (void)hipFree(dsel);
     return MH_OK;
 }
 

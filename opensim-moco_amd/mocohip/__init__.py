@@ -8,6 +8,6 @@ from .model import (Axis, Body, Coordinate, CoordinateActuator, DataTable,  # no
                     DeGrooteFregly2016Muscle, ExternalForce, Function, Joint,
                     Model, PathPoint)
 from .problem import (MocoAccelerationTrackingGoal, MocoAngularVelocityTrackingGoal, MocoBounds, MocoControlGoal,  # noqa: F401
-                      MocoFinalTimeGoal, MocoJointReactionGoal, MocoOrientationTrackingGoal, MocoProblem, MocoStateTrackingGoal,
+                      MocoFinalTimeGoal, MocoJointReactionGoal, MocoOrientationTrackingGoal, MocoOutputGoal, MocoProblem, MocoStateTrackingGoal,
                       MocoSumSquaredStateGoal, MocoTranslationTrackingGoal)
 from .solver import HipNLP, MocoHipSolver, MocoStudy  # noqa: F401

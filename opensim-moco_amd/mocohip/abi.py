@@ -25,6 +25,19 @@ MH_GOAL_TRANSLATION_TRACKING, MH_GOAL_ORIENTATION_TRACKING = 9, 10   # 8: not as
 MH_GOAL_ANGULAR_VELOCITY_TRACKING = 12   # 11: not assigned
 MH_GOAL_JOINT_REACTION = 14   # 13: not assigned
 MH_GOAL_ACCELERATION_TRACKING = 15
+MH_GOAL_OUTPUT = 17   # 16: not assigned
+# enum mh_muscle_output: the outputs of a DeGrooteFregly2016Muscle, by id
+MUSCLE_OUTPUTS = (
+    "length", "lengthening_speed", "activation", "excitation", "fiber_length", "normalized_fiber_length",
+    "pennation_angle", "cos_pennation_angle", "tendon_length", "tendon_strain", "fiber_length_along_tendon",
+    "active_force_length_multiplier", "passive_force_multiplier", "fiber_velocity", "normalized_fiber_velocity",
+    "fiber_velocity_along_tendon", "tendon_velocity", "force_velocity_multiplier", "pennation_angular_velocity",
+    "fiber_force", "fiber_force_along_tendon", "active_fiber_force", "passive_fiber_force",
+    "active_fiber_force_along_tendon", "passive_fiber_force_along_tendon", "tendon_force",
+    "passive_fiber_elastic_force", "passive_fiber_elastic_force_along_tendon", "passive_fiber_damping_force",
+    "passive_fiber_damping_force_along_tendon", "fiber_active_power", "fiber_passive_power", "tendon_power",
+    "muscle_power")
+MH_MO_COUNT = len(MUSCLE_OUTPUTS)
 MH_HERMITE_SIMPSON, MH_TRAPEZOIDAL = 0, 1
 MH_DYNAMICS_EXPLICIT, MH_DYNAMICS_IMPLICIT = 0, 1
 MH_FD_CENTRAL, MH_FD_FORWARD, MH_FD_BACKWARD = 0, 1, 2
@@ -251,6 +264,7 @@ MOCOHIP_SYMBOLS = {
     "mh_eval_dae": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
     "mh_eval_joint_reaction": (i32, [C.c_void_p, i32, i32, P(f64), P(f64)]),
     "mh_eval_frame_accelerations": (i32, [C.c_void_p, i32, i32, P(f64), P(f64)]),
+    "mh_eval_muscle_outputs": (i32, [C.c_void_p, i32, P(i32), P(i32), i32, P(f64), P(f64)]),
     "mh_eval_path": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
     "mh_set_timing": (i32, [C.c_void_p, i32]),
     "mh_get_backend_flags": (i32, [C.c_void_p, C.c_char_p, i32]),

@@ -29,7 +29,7 @@ from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm,
                       MocoControlBoundConstraint, MocoControlGoal, MocoFrameDistanceConstraint,
                       MocoAccelerationTrackingGoal, MocoInitialActivationGoal, MocoJointReactionGoal,
                       FrameReference, MocoAngularVelocityTrackingGoal, MocoFinalTimeGoal, MocoMarkerFinalGoal, MocoMarkerTrackingGoal,
-                      MarkersReference, MocoOrientationTrackingGoal, MocoProblem, MocoStateTrackingGoal,
+                      MarkersReference, MocoOrientationTrackingGoal, MocoOutputGoal, MocoProblem, MocoStateTrackingGoal,
                       MocoTranslationTrackingGoal, PiecewiseLinearFunction)
 from .solver import MocoHipSolver, MocoStudy
 
@@ -900,7 +900,7 @@ def gait10dof18musc_track(num_mesh_intervals: int = 65, muscles: bool = False) -
 
 
 def gait10dof18musc_inverse(num_mesh_intervals: int = 25, fd_scheme: str = "forward",
-                            sparsity: str = "random", subject=None) -> MocoStudy:
+                            sparsity: str = "random", subject=None, output_paths=()) -> MocoStudy:
     """MocoInverse on gait10dof18musc (configs[4], one solve of the batch):
     kinematics prescribed by a PositionMotion of the coordinate trajectories
     (MocoInverse.cpp:46-66; GCVSpline degree 5, PositionMotion.cpp:121-155),
@@ -913,7 +913,9 @@ def gait10dof18musc_inverse(num_mesh_intervals: int = 25, fd_scheme: str = "forw
     bundled walking coordinate trajectories, clipped by 1e-3 at both ends
     (clip_time_range, MocoInverse.cpp:82-86).  ``subject`` = (length,
     mass) scales the model (scale_subject: one subject of a configs[4]
-    sweep; the same kinematics)."""
+    sweep; the same kinematics).  ``output_paths``: MocoInverse's property
+    (MocoInverse.cpp:133-139): the solution of solve() carries
+    analyze(solution, output_paths) as ``outputs``."""
     m = gait10dof18musc_model(tendon_compliance=True, tendon_dynamics="implicit")
     if subject is not None:
         m = scale_subject(m, *subject)
@@ -936,7 +938,9 @@ def gait10dof18musc_inverse(num_mesh_intervals: int = 25, fd_scheme: str = "forw
                       # MocoInverse convergence / constraint tolerance
                       # defaults (MocoInverse.cpp:38-39, 108-109)
                       optim_convergence_tolerance=1e-3, optim_constraint_tolerance=1e-3)
-    return MocoStudy(p, s)
+    st = MocoStudy(p, s)
+    st.output_paths = list(output_paths)
+    return st
 
 
 def wrapped_pendulum(num_mesh_intervals: int = 20, scheme: str = "hermite-simpson",
@@ -1300,3 +1304,65 @@ def gait10dof18musc_accel_track(num_mesh_intervals: int = 200, dynamics: str = "
 def gait10dof18musc_accel_track_few(num_mesh_intervals: int = 3, **kw) -> MocoStudy:
     """N = 3: gait10dof18musc_accel_track, for tests."""
     return gait10dof18musc_accel_track(num_mesh_intervals, **kw)
+
+
+# ---- MocoOutputGoal over muscle outputs -------------------------------------
+HANGING_MUSCLE_MASS = 0.5
+HANGING_MUSCLE_GRAVITY = 9.81
+
+
+def hanging_muscle(num_mesh_intervals: int = 5, tendon: str = "rigid", ignore_activation_dynamics: bool = False,
+                   ignore_passive_fiber_force: bool = False, dynamics: str = "explicit",
+                   scheme: str = "hermite-simpson", fd_scheme: str = "central", hold=None,
+                   fiber_damping: float = 0.01) -> MocoStudy:
+    """The hanging muscle of testMocoActuators.cpp (createHangingMuscleModel):
+    a 0.5 kg mass on a SliderJoint along x, gravity 9.81 along +x, hanging from
+    a DeGrooteFregly2016Muscle "actuator" that runs straight from the ground
+    origin to the body origin, so that the muscle-tendon length is the
+    coordinate "height" and its lengthening speed the coordinate's speed.
+    ``tendon``: "rigid", or the compliant tendon's dynamics mode "explicit" /
+    "implicit".  The goal is an effort goal; ``hold`` = a height: the position
+    is bounded to that value and the speed to 0 over [0, 0.5] s, and the goal is
+    a MocoOutputGoal on the tendon force divided by the mass (every feasible
+    point then carries the weight: the integral is g times the duration)."""
+    from .model import DeGrooteFregly2016Muscle, PathPoint
+    m = Model("hanging_muscle", gravity=(HANGING_MUSCLE_GRAVITY, 0, 0))
+    m.add_body(Body("body", HANGING_MUSCLE_MASS, (0, 0, 0), (0, 0, 0, 0, 0, 0)))
+    height = Coordinate("height", (0.0, 0.3), "translational")
+    m.add_joint(Joint.slider("joint", "ground", "body", height))
+    mu = DeGrooteFregly2016Muscle("actuator", [PathPoint("ground", (0, 0, 0), name="origin"),
+                                               PathPoint("body", (0, 0, 0), name="insertion")],
+                                  max_isometric_force=30.0, optimal_fiber_length=0.10, tendon_slack_length=0.05,
+                                  pennation_angle_at_optimal=0.1, max_contraction_velocity=10.0,
+                                  fiber_damping=fiber_damping, tendon_strain_at_one_norm_force=0.10)
+    mu.ignore_tendon_compliance = tendon == "rigid"
+    mu.tendon_compliance_dynamics_mode = "implicit" if tendon == "implicit" else "explicit"
+    mu.ignore_activation_dynamics = ignore_activation_dynamics
+    mu.ignore_passive_fiber_force = ignore_passive_fiber_force
+    m.add_muscle(mu)
+    p = MocoProblem(m)
+    if hold is None:
+        p.set_time_bounds(0.0, (0.05, 1.0))
+        p.set_state_info("/jointset/joint/height/value", (0.10, 0.20), 0.15, 0.14)
+        p.set_state_info("/jointset/joint/height/speed", (-1.0, 1.0), 0.0, 0.0)
+        p.add_goal(MocoControlGoal("effort", 1.0))
+    else:
+        p.set_time_bounds(0.0, 0.5)
+        p.set_state_info("/jointset/joint/height/value", (float(hold), float(hold)))
+        p.set_state_info("/jointset/joint/height/speed", (0.0, 0.0))
+        p.add_goal(MocoOutputGoal("carried_weight", 1.0, output_path="/forceset/actuator|tendon_force",
+                                  divide_by_mass=True))
+    s = MocoHipSolver(num_mesh_intervals=num_mesh_intervals, transcription_scheme=scheme,
+                      optim_finite_difference_scheme=fd_scheme, multibody_dynamics_mode=dynamics)
+    return MocoStudy(p, s)
+
+
+def gait10dof18musc_muscle_outputs(num_mesh_intervals: int = 200, output: str = "active_fiber_force",
+                                   weight: float = 1e-4, **kw) -> MocoStudy:
+    """gait10dof18musc's study with one MocoOutputGoal per muscle on ``output``
+    (18 goals, before the effort goal): the profile's workload."""
+    st = gait10dof18musc(num_mesh_intervals, **kw)
+    for mu in st.problem.model.muscles:
+        st.problem.goals.insert(len(st.problem.goals) - 1,
+                                MocoOutputGoal(f"{output}_{mu.name}", weight, output_path=f"{mu.path}|{output}"))
+    return st

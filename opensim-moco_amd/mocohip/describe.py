@@ -18,7 +18,7 @@ from .problem import (Constant, GCVSpline, ImplicitAuxiliaryDerivativesTerm, Moc
                       MocoControlGoal, MocoFinalTimeGoal, MocoFrameDistanceConstraint, MocoInitialActivationGoal,
                       MocoAccelerationTrackingGoal, MocoAngularVelocityTrackingGoal, MocoJointReactionGoal,
                       MocoMarkerFinalGoal, MocoMarkerTrackingGoal, MocoOrientationTrackingGoal,
-                      MocoTranslationTrackingGoal,
+                      MocoOutputGoal, MocoTranslationTrackingGoal,
                       MocoStateTrackingGoal, MocoSumSquaredStateGoal, PiecewiseLinearFunction)
 from .splines import gcv_interpolating_ppoly
 
@@ -192,6 +192,9 @@ def describe(study) -> str:
                                  _s(g.loads_frame), _s(g.expressed_in_frame_path), str(len(g.reaction_measures))]
                                 + [_s(m) for m in g.reaction_measures] + [str(len(w))]
                                 + [f"{_s(k)} {_d(v)}" for k, v in w]))
+        elif isinstance(g, MocoOutputGoal):
+            out.append(" ".join(["goal", "output", _s(g.name), _d(g.weight), _s(g.output_path),
+                                 str(int(bool(g.divide_by_mass))), str(int(bool(g.divide_by_displacement)))]))
         elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
             out.append(f"goal aux_derivatives {_s(g.name)} {_d(g.weight)}")
         else:

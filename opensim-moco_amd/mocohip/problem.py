@@ -473,6 +473,57 @@ class MocoJointReactionGoal:
         return w
 
 
+def parse_muscle_output_path(model, output_path: str):
+    """(muscle index, output id) of an output path ``<component>|<output>`` of
+    a DeGrooteFregly2016Muscle: ``/forceset/<muscle>|<output>`` with an output
+    of abi.MUSCLE_OUTPUTS (include/mocohip.h enum mh_muscle_output), or its
+    path's ``/forceset/<muscle>/geometrypath|length`` / ``|lengthening_speed``.
+    ValueError, naming the supported outputs, for any other component or
+    output."""
+    supported = ("supported: the outputs " + ", ".join(abi.MUSCLE_OUTPUTS) + " of a DeGrooteFregly2016Muscle "
+                 "(<muscle path>|<output>; length and lengthening_speed also as <muscle path>/geometrypath|...)")
+    comp, sep, out = output_path.partition("|")
+    if not sep or not out:
+        raise ValueError(f"output path '{output_path}' is not of the form <component path>|<output>; {supported}")
+    path_output = comp.endswith("/geometrypath")
+    if path_output:
+        comp = comp[:-len("/geometrypath")]
+    im = next((i for i, mu in enumerate(model.muscles) if comp in (mu.path, mu.name)), None)
+    if im is None:
+        raise ValueError(f"output path '{output_path}': component '{comp}' is not a DeGrooteFregly2016Muscle of "
+                         f"the model; {supported}")
+    if out not in abi.MUSCLE_OUTPUTS or (path_output and out not in abi.MUSCLE_OUTPUTS[:2]):
+        raise ValueError(f"output path '{output_path}': no supported output '{out}'; {supported}")
+    return im, abi.MUSCLE_OUTPUTS.index(out)
+
+
+@dataclass
+class MocoOutputGoal:
+    """MocoOutputGoal (Moco/Moco/MocoGoal/MocoOutputGoal.{h,cpp}): the integral
+    over the phase of one scalar model output, times the weight, divided by the
+    model's total mass with ``divide_by_mass`` (include/mocohip.h
+    MH_GOAL_OUTPUT).  ``output_path``: an output of a DeGrooteFregly2016Muscle
+    (parse_muscle_output_path), e.g. "/forceset/soleus_r|tendon_force"; outputs
+    of other components are a follow-up.  ``divide_by_displacement`` needs the
+    reference's calcSystemDisplacement (the displacement of the whole system's
+    mass center between the initial and the final state), which is not
+    available: NotImplementedError, a follow-up."""
+    name: str = "output"
+    weight: float = 1.0
+    output_path: str = ""
+    divide_by_mass: bool = False
+    divide_by_displacement: bool = False
+
+    def set_output_path(self, path: str):
+        self.output_path = path
+
+    def set_divide_by_mass(self, on: bool):
+        self.divide_by_mass = bool(on)
+
+    def set_divide_by_displacement(self, on: bool):
+        self.divide_by_displacement = bool(on)
+
+
 # ------------------------------------------------- functions of time ----
 @dataclass
 class Constant:
@@ -834,6 +885,25 @@ class ProblemRep:
                     raise NotImplementedError("MocoJointReactionGoal with MocoParameters "
                                               "(the load reads the mass properties)")
                 self._joint_reaction_terms(model, g, gs, gidx, gcol, gw)
+            elif isinstance(g, MocoOutputGoal):
+                # MocoOutputGoal::initializeOnModelImpl's check, then one term:
+                # the muscle, the output, the divisor (Model::getTotalMass)
+                if not g.output_path:
+                    raise ValueError("No output_path provided.")
+                if g.divide_by_displacement:
+                    raise NotImplementedError("MocoOutputGoal with divide_by_displacement "
+                                              "(calcSystemDisplacement is not available)")
+                if problem.parameters:
+                    raise NotImplementedError("MocoOutputGoal with MocoParameters "
+                                              "(the goals' gradient along a parameter is defined as 0)")
+                im, which = parse_muscle_output_path(model, g.output_path)
+                den = 1.0
+                if g.divide_by_mass:
+                    den = 0.0
+                    for body in model.bodies.values():
+                        den += float(body.mass)
+                gs.kind = abi.MH_GOAL_OUTPUT
+                gidx.append(im); gcol.append(which); gw.append(den)
             elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
                 gs.kind = abi.MH_GOAL_AUX_DERIVATIVES
                 naux = sum(1 for m in model.muscles if not m.ignore_tendon_compliance

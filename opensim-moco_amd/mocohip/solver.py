@@ -20,6 +20,7 @@ from typing import Optional
 import numpy as np
 
 from . import abi
+from .model import DataTable
 from .problem import MocoProblem, ProblemRep
 
 _SCHEMES = {"hermite-simpson": abi.MH_HERMITE_SIMPSON,
@@ -638,6 +639,51 @@ class HipNLP(_NLPBase):
         t = x[0] + (x[1] - x[0]) * grid
         return self.eval_frame_accelerations(names.index(goal_name), np.column_stack([t, self.point_inputs(x)]))
 
+    def eval_muscle_outputs(self, muscles, outputs, inputs: np.ndarray) -> np.ndarray:
+        """Rows [t, point inputs] (as eval_dae) -> [rows, len(muscles)]:
+        output ``outputs[k]`` (its id in abi.MUSCLE_OUTPUTS) of muscle
+        ``muscles[k]`` (its index among the model's muscles) at every row
+        (mh_eval_muscle_outputs).  Not tied to a goal."""
+        inputs = np.ascontiguousarray(inputs, float)
+        mus = np.ascontiguousarray(muscles, np.int32).reshape(-1)
+        which = np.ascontiguousarray(outputs, np.int32).reshape(-1)
+        assert inputs.ndim == 2 and inputs.shape[1] == 1 + self.NI and len(mus) == len(which)
+        npts = inputs.shape[0]
+        out = np.empty((max(npts, 1), max(len(mus), 1)))
+        self._check(self._fn("eval_muscle_outputs")(self.ctx, len(mus), abi.iptr(mus), abi.iptr(which), npts,
+                                                    abi.dptr(inputs), abi.dptr(out)))
+        return out[:npts, :len(mus)]
+
+    def muscle_outputs(self, trajectory, paths, with_times: bool = False):
+        """(labels, values [grid points, len(labels)]): the muscle outputs
+        whose paths match ``paths`` at every grid point of ``trajectory`` (a
+        MocoTrajectory on this NLP's grid, or an iterate x); with_times: (times,
+        labels, values).  Each entry of
+        ``paths`` is a regular expression matched against the whole path of
+        every supported output, "<muscle path>|<output>" and "<muscle
+        path>/geometrypath|length" / "|lengthening_speed", as the reference's
+        analyze() matches its arguments against the model's outputs
+        (MocoUtilities.h:277-305): outputs in model order, muscles first, one
+        column per matching output."""
+        import re
+        from .problem import parse_muscle_output_path
+        from .trajectory import nlp_grid
+        model = self.rep.problem.model
+        pats = [re.compile(p) for p in paths]
+        labels = []
+        for mu in model.muscles:
+            own = [f"{mu.path}|{o}" for o in abi.MUSCLE_OUTPUTS[2:]]
+            own += [f"{mu.path}/geometrypath|{o}" for o in abi.MUSCLE_OUTPUTS[:2]]
+            labels += [c for c in own if any(p.fullmatch(c) for p in pats)]
+        x = trajectory.to_iterate(self) if hasattr(trajectory, "to_iterate") else np.asarray(trajectory, float)
+        t = x[0] + (x[1] - x[0]) * nlp_grid(self)
+        vals = np.zeros((len(t), 0))
+        if labels:
+            sel = [parse_muscle_output_path(model, c) for c in labels]
+            vals = self.eval_muscle_outputs([s[0] for s in sel], [s[1] for s in sel],
+                                            np.column_stack([t, self.point_inputs(x)]))
+        return (t, labels, vals) if with_times else (labels, vals)
+
     def eval_g(self, x, new_x=True):
         x = np.ascontiguousarray(x, float)
         g = np.empty(max(self.row_end - self.row_begin, 1))
@@ -826,6 +872,9 @@ class MocoStudy:
                  solver: Optional[MocoHipSolver] = None):
         self.problem = problem or MocoProblem()
         self.solver = solver or MocoHipSolver()
+        # MocoInverse's output_paths (MocoInverse.cpp:133-139): solve() attaches
+        # analyze(solution, output_paths) to the solution as ``outputs``
+        self.output_paths = []
 
     def init_solver(self) -> MocoHipSolver:
         self.solver = MocoHipSolver()
@@ -872,6 +921,7 @@ class MocoStudy:
                 names = list(getattr(nlp.rep, "goal_names", []))
                 r.objective_breakdown = [(names[i] if i < len(names) else f"goal_{i}", float(v))
                                          for i, v in enumerate(terms)]
+            outputs = self.analyze(sol, self.output_paths, nlp) if self.output_paths else None
         finally:
             if own:
                 nlp.close()
@@ -879,4 +929,26 @@ class MocoStudy:
                              "num_iterations": str(r.iterations), "solver_duration": repr(r.duration),
                              "status": r.status, "optimizer": r.optimizer + " over the C ABI"})
         sol.stats = r
+        sol.outputs = outputs
         return sol
+
+    def analyze(self, trajectory, output_paths, nlp=None) -> DataTable:
+        """MocoStudy::analyze (MocoStudy.cpp:110; MocoUtilities.h:277-360): the
+        outputs whose paths match ``output_paths`` (regular expressions, e.g.
+        ".*tendon_force") along ``trajectory``, as a DataTable with the
+        trajectory's times and one column per matching output, labelled with
+        the output's path; trajectory.write_table / read_table store it as an
+        .sto file.  The outputs are those of the problem's
+        DeGrooteFregly2016Muscles (HipNLP.muscle_outputs); prescribed
+        kinematics are applied, parameters are not."""
+        own = nlp is None
+        nlp = nlp or self.create_nlp()
+        if not hasattr(nlp, "muscle_outputs"):
+            raise TypeError(f"analyze / output_paths need a HipNLP: {type(nlp).__name__} does not evaluate muscle "
+                            "outputs")
+        try:
+            t, labels, vals = nlp.muscle_outputs(trajectory, output_paths, with_times=True)
+        finally:
+            if own:
+                nlp.close()
+        return DataTable("analysis", t, {c: vals[:, i].copy() for i, c in enumerate(labels)})

@@ -27,7 +27,7 @@ Layout (little endian, x86-64 struct layout of include/mocohip.h):
   MH_GOAL_MARKER_TRACKING goal (kind 7) needs no newer version, as the
   frame-distance path kinds needed none; nor do the frame-tracking goals
   (kinds 9, 10 and 12), nor the joint-reaction goal (kind 14), nor the
-  acceleration-tracking goal (kind 15).  Offset frames do not travel: their translations and orientations are in the goals' terms."""
+  acceleration-tracking goal (kind 15), nor the output goal (kind 17).  Offset frames do not travel: their translations and orientations are in the goals' terms."""
 from __future__ import annotations
 
 import ctypes as C

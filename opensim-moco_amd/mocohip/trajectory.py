@@ -426,3 +426,34 @@ def _num(v: float) -> str:
     if math.isinf(v):
         return "Inf" if v > 0 else "-Inf"
     return repr(float(v))
+
+
+# ---- TimeSeriesTable .sto I/O (MocoStudy.analyze's result) -------------------
+def write_table(table, path: str):
+    """A DataTable (model.DataTable: name, times, columns) as an .sto file in
+    the layout MocoTrajectory.write uses: a name line, the header, endheader,
+    the tab-separated labels after "time", one row per time."""
+    labels = list(table.columns)
+    lines = [table.name or "table", "DataType=double", "version=3", "endheader", "\t".join(["time"] + labels)]
+    for i, t in enumerate(np.asarray(table.times, float)):
+        lines.append("\t".join(_num(v) for v in [t] + [table.columns[c][i] for c in labels]))
+    with open(path, "w") as fh:
+        fh.write("\n".join(lines) + "\n")
+
+
+def read_table(path: str):
+    """The DataTable that write_table wrote (any .sto with a "time" column)."""
+    from .model import DataTable
+    with open(path) as fh:
+        lines = fh.read().splitlines()
+    i = 0
+    while i < len(lines) and lines[i].strip().lower() != "endheader":
+        i += 1
+    if i >= len(lines):
+        raise ValueError(f"{path}: no endheader")
+    labels = [s.strip() for s in lines[i + 1].split("\t") if s.strip() != ""]
+    if not labels or labels[0] != "time":
+        raise ValueError(f"{path}: first column must be time")
+    rows = [[float(v) for v in ln.split()] for ln in lines[i + 2:] if ln.strip()]
+    data = np.array(rows, float).reshape(len(rows), len(labels))
+    return DataTable(lines[0].strip(), data[:, 0], {c: data[:, 1 + k] for k, c in enumerate(labels[1:])})
