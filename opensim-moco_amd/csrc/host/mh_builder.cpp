@@ -818,6 +818,8 @@ void make_rep(const Problem& P, ProblemRep& R) {
             gs.kind = MH_GOAL_CONTROL;
             gs.exponent = g.exponent;
             if (gs.exponent < 2) fail("Exponent must be 2 or greater.");
+            for (auto& kv : g.weights)   // MocoControlGoal.cpp:64-71
+                if (cidx(kv.first) < 0) fail("Unrecognized control '" + kv.first + "'.");
             for (auto& n : R.control_names) {
                 const double w = weight(g.weights, n);
                 if (w != 0.0) term(cidx(n), -1, w);
@@ -825,6 +827,9 @@ void make_rep(const Problem& P, ProblemRep& R) {
             break;
         case Goal::STATE_TRACKING: {
             gs.kind = MH_GOAL_STATE_TRACKING;
+            for (auto& kv : g.weights)   // MocoStateTrackingGoal.cpp:45-52
+                if (sidx(kv.first) < 0)
+                    fail("Weight provided with name '" + kv.first + "' but this is not a recognized state.");
             const int ti = lookup(R.cm.table_index, g.table);
             if (ti < 0) fail("reference table " + g.table + " not in model");
             gs.table = R.cm.table_index[ti].second;
@@ -1064,6 +1069,9 @@ void make_rep(const Problem& P, ProblemRep& R) {
         }
         case Goal::SUM_SQUARED_STATE:
             gs.kind = MH_GOAL_SUM_SQUARED_STATE;
+            for (auto& kv : g.weights)   // MocoSumSquaredStateGoal.cpp:37-45
+                if (sidx(kv.first) < 0)
+                    fail("Weight provided with name '" + kv.first + "' but this is not a recognized state.");
             for (auto& n : R.state_names) {
                 const double w = weight(g.weights, n);
                 if (w != 0.0) term(sidx(n), -1, w);

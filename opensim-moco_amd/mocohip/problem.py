@@ -827,12 +827,19 @@ class ProblemRep:
                 gs.exponent = int(g.exponent)
                 if gs.exponent < 2:
                     raise ValueError("Exponent must be 2 or greater.")
+                for n in g.control_weights:   # MocoControlGoal.cpp:64-71
+                    if n not in cidx:
+                        raise ValueError(f"Unrecognized control '{n}'.")
                 for n in self.control_names:
                     w = float(g.control_weights.get(n, 1.0))
                     if w != 0.0:
                         gidx.append(cidx[n]); gcol.append(-1); gw.append(w)
             elif isinstance(g, MocoStateTrackingGoal):
                 gs.kind = abi.MH_GOAL_STATE_TRACKING
+                for n in g.state_weights:   # MocoStateTrackingGoal.cpp:45-52
+                    if n not in sidx:
+                        raise ValueError(f"Weight provided with name '{n}' but this is not a "
+                                         "recognized state.")
                 ref = g.reference
                 if ref.name not in self.compiled.table_index:
                     raise ValueError(f"reference table {ref.name} not in model")
@@ -912,6 +919,10 @@ class ProblemRep:
                     gidx.append(k); gcol.append(-1); gw.append(1.0)
             elif isinstance(g, MocoSumSquaredStateGoal):
                 gs.kind = abi.MH_GOAL_SUM_SQUARED_STATE
+                for n in g.state_weights:   # MocoSumSquaredStateGoal.cpp:37-45
+                    if n not in sidx:
+                        raise ValueError(f"Weight provided with name '{n}' but this is not a "
+                                         "recognized state.")
                 for n in self.state_names:
                     w = float(g.state_weights.get(n, 1.0))
                     if w != 0.0:

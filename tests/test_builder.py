@@ -15,7 +15,8 @@ import pytest
 
 from mocohip import configs
 from mocohip.describe import write_description
-from mocohip.problem import Constant, GCVSpline, MocoControlBoundConstraint, PiecewiseLinearFunction
+from mocohip.problem import (Constant, GCVSpline, MocoControlBoundConstraint, MocoControlGoal, MocoFinalTimeGoal,
+                             MocoStateTrackingGoal, MocoSumSquaredStateGoal, PiecewiseLinearFunction)
 from mocohip.tape import write_tape
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -47,6 +48,12 @@ def _bounded_pendulum(kind):
     return st
 
 
+def _pendulum_goals(goals):
+    st = configs.double_pendulum(5)
+    st.problem.goals = goals
+    return st
+
+
 STUDIES = {
     "sliding_mass": lambda: configs.sliding_mass(7),
     "double_pendulum_swingup": lambda: configs.double_pendulum_swingup(9),
@@ -69,6 +76,16 @@ STUDIES = {
     # tape v8: MocoParameters on a body mass / two springs' stiffness
     "oscillator_mass": lambda: configs.oscillator_mass(6),
     "oscillator_two_springs": lambda: configs.oscillator_two_springs(6),
+    # goal lowerings no bundled study carries: MocoSumSquaredStateGoal with a
+    # zero weight (a dropped term), two MocoControlGoals with exponents 3 and
+    # 4, a goal whose weights are all 0 (no terms)
+    "pendulum_sum_squared_state": lambda: _pendulum_goals([
+        MocoFinalTimeGoal(weight=0.001),
+        MocoSumSquaredStateGoal("states", 0.3, {"/jointset/j0/q0/value": 0.0, "/jointset/j1/q1/speed": 3.0})]),
+    "pendulum_two_control_goals": lambda: _pendulum_goals([
+        MocoControlGoal("effort3", 0.7, 3, {"/tau0": 0.0}), MocoControlGoal("effort4", 1e-3, 4, {"/tau1": 2.5})]),
+    "pendulum_all_zero_weights": lambda: _pendulum_goals([
+        MocoControlGoal("dropped", 2.0, 2, {"/tau0": 0.0, "/tau1": 0.0}), MocoFinalTimeGoal(weight=0.25)]),
 }
 
 
@@ -99,7 +116,8 @@ def test_cpp_builder_shard_options(tmp_path):
 
 def test_cpp_builder_reports_the_reference_errors(tmp_path):
     """The reference's input checks (MocoControlBoundConstraint.cpp:38-118,
-    MocoControlGoal exponent) raise in the C++ builder too."""
+    MocoControlGoal exponent and weight names, MocoSumSquaredStateGoal and
+    MocoStateTrackingGoal weight names) raise in the C++ builder too."""
     cases = []
     st = configs.double_pendulum(4)
     pc = MocoControlBoundConstraint()
@@ -128,6 +146,18 @@ def test_cpp_builder_reports_the_reference_errors(tmp_path):
     st = configs.oscillator_mass(4)
     st.problem.parameters[0].property_name = "stiffness"
     cases.append((st, "has no property 'stiffness'"))
+    # a weight for a control / state the model does not have
+    # (MocoControlGoal.cpp:64-71, MocoSumSquaredStateGoal.cpp:37-45,
+    # MocoStateTrackingGoal.cpp:45-52)
+    cases.append((_pendulum_goals([MocoControlGoal("effort", 1.0, 2, {"/tau2": 3.0})]),
+                  "Unrecognized control '/tau2'."))
+    cases.append((_pendulum_goals([MocoSumSquaredStateGoal("states", 1.0, {"/jointset/j0/q0/valu": 3.0})]),
+                  "Weight provided with name '/jointset/j0/q0/valu' but this is not a recognized state."))
+    st = configs.double_pendulum(4)
+    tab = configs.double_pendulum_swing_states()
+    st.problem.model.add_table(tab)
+    st.problem.goals = [MocoStateTrackingGoal("tracking", 1.0, tab, {"/jointset/j2/q2/value": 3.0})]
+    cases.append((st, "Weight provided with name '/jointset/j2/q2/value' but this is not a recognized state."))
     for i, (st, msg) in enumerate(cases):
         desc = tmp_path / f"e{i}.mhdesc"
         write_description(st, str(desc))

@@ -576,7 +576,8 @@ def test_eval_jac_g(name, backend):
                                   "gait_rigid_implicit", "gait_inverse", "pendulum_bound_both_implicit",
                                   "double_pendulum_swingup", "double_pendulum_swingup_implicit_central",
                                   "coupled_pendulum", "coupled_pendulum_implicit", "wrapped_pendulum",
-                                  "rajagopal18_inverse", "rajagopal80"])
+                                  "rajagopal18_inverse", "rajagopal80",
+                                  "gait_rigid_backward", "gait_implicit_both_central"])
 def test_objective_and_gradient(name):
     gpu, ref, st = _pair(name)
     for _, x in _iterates(gpu):
