@@ -601,7 +601,92 @@ enum mh_goal_kind {
      * derivative variable.  Every other entry keeps its bits.  Goals of this
      * kind on one problem share one launch.  mh_batch_* accepts contexts with
      * such goals and never reads them, as for every other goal. */
-    MH_GOAL_OUTPUT = 17
+    MH_GOAL_OUTPUT = 17,
+    /* MocoOutputGoal over one output of a Bhargava2004Metabolics component
+     * (Bhargava2004Metabolics.cpp:217-250, 337-537; enum mh_metabolics_output):
+     *     weight * duration * quadrature over every grid point of
+     *         L = value of the output / divisor
+     * The component travels in the goal's terms, 6 + 6 nm of them for a
+     * component of nm >= 1 muscles (mh_goal.exponent and mh_goal.table are
+     * unused).  Header terms tb .. tb + 5:
+     *   goal_index[tb]      option flags: 1 use_smoothing, 2 the Huber form (with
+     *                       1 only; otherwise tanh), 4 force-dependent shortening
+     *                       constant, 8 include negative mechanical work,
+     *                       16 forbid negative total power, 32 minimum heat rate
+     *                       per muscle
+     *   goal_column[tb]     the output (enum mh_metabolics_output)
+     *   goal_column[tb + 1] the position, among the component's muscles, of the
+     *                       channel of MH_MET_MUSCLE_METABOLIC_RATE; -1 for
+     *                       every other output
+     *   goal_weight[tb ..]  the divisor (1.0, or the model's total mass for
+     *                       divide_by_mass: positive and finite), the basal rate
+     *                       B = basal_coefficient * total mass ^ basal_exponent
+     *                       (formed by the host; finite), the muscle effort
+     *                       scaling factor s (finite), the velocity, power and
+     *                       heat-rate smoothing ks (each positive and finite)
+     * then per muscle, in the component's order, terms mb .. mb + 5:
+     *   goal_index[mb]      the muscle
+     *   goal_weight[mb ..]  its mass m (positive and finite), slow-twitch ratio r
+     *                       (in [0, 1]), activation constants slow / fast As, Af
+     *                       and maintenance constants slow / fast Ms, Mf (finite)
+     * Every goal_index / goal_column not named above is 0.
+     * Per muscle, with a = the activation and e = the excitation as
+     * MH_GOAL_OUTPUT defines them (e is the muscle's control; a is the control
+     * too when activation dynamics are ignored), and the muscle's
+     * active_fiber_force Fa, passive_fiber_force Fp, normalized_fiber_length,
+     * fiber_velocity v and active_force_length_multiplier fAL of enum
+     * mh_muscle_output from one evaluation, every operation rounded on its own
+     * in the order written:
+     *   A = s a;  E = s e;  FA = s Fa;  FT = FA + Fp;  ve = v + 1e-16
+     *   slow = r sin(pi/2 E);  fast = (1 - r) (1 - cos(pi/2 E))
+     *   activation rate  = m (As slow + Af fast)
+     *   maintenance rate = m d (Ms slow + Mf fast), d the piecewise-linear curve
+     *       through (0, .5) (.5, .5) (1, 1) (1.5, 0) (10, 0) at the normalized
+     *       fibre length
+     *   alpha = cond(ve; .25 FT, 0; kv, -1), or with flag 4
+     *           cond'(ve; .16 (A fAL Fmax) + .18 FT, .157 FT; kv)
+     *   shortening rate = -alpha ve
+     *   work rate = -FA v with flag 8, else cond(ve; -FA v, 0; kv, -1)
+     *   flag 16: P = activation + maintenance + shortening + work; the
+     *       shortening rate -= cond(-P; 0, P; kp, +1) (smoothing) or P where
+     *       P < 0 (no smoothing)
+     *   heat = activation + maintenance + shortening;  flag 32: heat =
+     *       cond(m - heat; heat, m; kh, +1) (as -heat + m), or m where heat < m
+     *   metabolic rate = heat + work
+     * cond(c; left, right; k, dir) = left where c <= 0, else right (no
+     * smoothing); left + (right - left) (1/2 + 1/2 tanh(k c)) (tanh); with the
+     * Huber form, y = k (dir c + 1 / (2 k)), f = o (y < 0), y^2 / 2 + o (y <= 1),
+     * y - 1/2 + o otherwise, o = left (dir = +1) or right: the value is
+     * (right - left) / c * (f / k + o (1 - 1 / k)).  cond' is the tanh form
+     * whenever smoothing is on.
+     * The total_* outputs sum the muscles' rates in the component's order;
+     * total_metabolic_rate then adds B once; muscle_metabolic_rate is one
+     * muscle's metabolic rate.  The result is divided by the divisor last.
+     * A velocity-stage goal like MH_GOAL_OUTPUT, accepted wherever that is; not
+     * with MocoParameters (MH_ERR_UNSUPPORTED).  A malformed block (fewer than
+     * 12 terms, a count that is not 6 + 6 nm, a nonzero unused index or column),
+     * unknown flags or output, a channel or a muscle out of range, or a number
+     * outside the ranges above: MH_ERR_INVALID.
+     * Gradient: finite-difference quotients of L (the quotient of the sums)
+     * with k_grad's formulas, added to the entries the other goals wrote, over
+     * t0, tf and the point inputs MH_GOAL_OUTPUT's gradient reads for any of
+     * the goal's muscles, each muscle's excitation control always among them.
+     * A muscle that a direction cannot change enters that direction's sum with
+     * its unperturbed value.  Every other entry keeps its bits.  Goals of this
+     * kind on one problem share one launch.  mh_batch_* accepts contexts with
+     * such goals and never reads them, as for every other goal. */
+    MH_GOAL_METABOLICS = 18
+};
+/* The outputs of a Bhargava2004Metabolics component (Bhargava2004Metabolics.h)
+ * that MH_GOAL_METABOLICS integrates. */
+enum mh_metabolics_output {
+    MH_MET_TOTAL_METABOLIC_RATE = 0,
+    MH_MET_TOTAL_ACTIVATION_RATE = 1,
+    MH_MET_TOTAL_MAINTENANCE_RATE = 2,
+    MH_MET_TOTAL_SHORTENING_RATE = 3,
+    MH_MET_TOTAL_MECHANICAL_WORK_RATE = 4,
+    MH_MET_MUSCLE_METABOLIC_RATE = 5,   /* the list output, one channel */
+    MH_MET_COUNT = 6
 };
 /* The outputs of a DeGrooteFregly2016Muscle that MH_GOAL_OUTPUT integrates and
  * mh_eval_muscle_outputs reads.  Ids 0 and 1 are its GeometryPath's outputs
@@ -1139,6 +1224,18 @@ int mh_eval_frame_accelerations(mh_ctx* ctx, int32_t goal, int32_t npoints, cons
  * MH_ERR_UNSUPPORTED.  Synchronous. */
 int mh_eval_muscle_outputs(mh_ctx* ctx, int32_t nout, const int32_t* muscle, const int32_t* output,
         int32_t npoints, const double* inputs, double* out);
+/* A Bhargava2004Metabolics component at npoints rows [time, NI point inputs]:
+ * the component is given as a goal of kind MH_GOAL_METABOLICS carries it, nterms
+ * = 6 + 6 nm terms (index, column, weight; the output, channel and divisor are
+ * not read), and out[row] = [total_metabolic_rate (with the basal rate),
+ * total_activation_rate, total_maintenance_rate, total_shortening_rate,
+ * total_mechanical_work_rate, then the metabolic rate of each of the nm
+ * muscles]: 5 + nm values, before any divisor.  Not tied to a goal: any
+ * context serves.  npoints <= 0 or a block the goal would refuse:
+ * MH_ERR_INVALID; a problem with MocoParameters: MH_ERR_UNSUPPORTED.
+ * Synchronous. */
+int mh_eval_metabolics(mh_ctx* ctx, int32_t nterms, const int32_t* index, const int32_t* column,
+        const double* weight, int32_t npoints, const double* inputs, double* out);
 /* Path-constraint probe, the counterpart of mh_eval_dae for the path
  * callback: the npath path-equation values of npoints probe rows [time, point
  * inputs (NS + NC + NDV + ...)] (the row of mh_get_callback_sparsity, W

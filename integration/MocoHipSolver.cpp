@@ -26,6 +26,7 @@
 #include <OpenSim/Common/PiecewiseLinearFunction.h>
 #include <OpenSim/Common/SimmSpline.h>
 #include <OpenSim/Common/Stopwatch.h>
+#include <OpenSim/Moco/Components/Bhargava2004Metabolics.h>
 #include <OpenSim/Moco/Components/DeGrooteFregly2016Muscle.h>
 #include <OpenSim/Moco/Components/PositionMotion.h>
 #include <OpenSim/Moco/MocoGoal/MocoControlGoal.h>
@@ -714,6 +715,52 @@ mhb::Problem OpenSim::compileProblemRep(const MocoProblemRep& rep) {
                     g.getName());
             OPENSIM_THROW_IF(hg.output_path.empty(), Exception, "No output_path provided.");
             std::string comp = hg.output_path.substr(0, hg.output_path.find('|'));
+            if (model.hasComponent<Bhargava2004Metabolics>(comp)) {
+                // an output of a Bhargava2004Metabolics: the component travels
+                // with the goal (mhb::MetabolicsComponent; make_rep lowers it to
+                // MH_GOAL_METABOLICS and checks the output's name and channel).
+                // The path handed on is /<name>|<output>, the form make_rep
+                // matches, wherever the component sits in the model.
+                const auto& met = model.getComponent<Bhargava2004Metabolics>(comp);
+                mhb::MetabolicsComponent& mc = hg.metabolics;
+                hg.has_metabolics = true;
+                mc.name = met.getName();
+                hg.output_path = "/" + mc.name + hg.output_path.substr(hg.output_path.find('|'));
+                mc.enforce_minimum_heat_rate_per_muscle = met.get_enforce_minimum_heat_rate_per_muscle();
+                mc.use_force_dependent_shortening_prop_constant =
+                        met.get_use_force_dependent_shortening_prop_constant();
+                mc.basal_coefficient = met.get_basal_coefficient();
+                mc.basal_exponent = met.get_basal_exponent();
+                mc.muscle_effort_scaling_factor = met.get_muscle_effort_scaling_factor();
+                mc.include_negative_mechanical_work = met.get_include_negative_mechanical_work();
+                mc.forbid_negative_total_power = met.get_forbid_negative_total_power();
+                mc.use_smoothing = met.get_use_smoothing();
+                mc.smoothing_type = met.get_smoothing_type();
+                mc.velocity_smoothing = met.get_velocity_smoothing();
+                mc.power_smoothing = met.get_power_smoothing();
+                mc.heat_rate_smoothing = met.get_heat_rate_smoothing();
+                for (int i = 0; i < met.getProperty_muscle_parameters().size(); ++i) {
+                    const auto& p = met.get_muscle_parameters(i);
+                    const auto* dgf = dynamic_cast<const DeGrooteFregly2016Muscle*>(&p.getMuscle());
+                    OPENSIM_THROW_IF(!dgf, Exception,
+                            "MocoHipSolver: goal '{}': muscle '{}' of '{}' is not a DeGrooteFregly2016Muscle",
+                            g.getName(), p.getName(), comp);
+                    mhb::MetabolicsMuscle mp;
+                    mp.name = p.getName();
+                    mp.muscle_path = dgf->getAbsolutePathString();
+                    mp.ratio_slow_twitch_fibers = p.get_ratio_slow_twitch_fibers();
+                    mp.specific_tension = p.get_specific_tension();
+                    mp.density = p.get_density();
+                    mp.activation_constant_slow_twitch = p.get_activation_constant_slow_twitch();
+                    mp.activation_constant_fast_twitch = p.get_activation_constant_fast_twitch();
+                    mp.maintenance_constant_slow_twitch = p.get_maintenance_constant_slow_twitch();
+                    mp.maintenance_constant_fast_twitch = p.get_maintenance_constant_fast_twitch();
+                    if (p.get_use_provided_muscle_mass()) mp.muscle_mass = p.get_provided_muscle_mass();
+                    mc.muscles.push_back(mp);
+                }
+                prob.goals.push_back(hg);
+                return;
+            }
             const std::string gp = "/geometrypath";
             if (comp.size() >= gp.size() && comp.compare(comp.size() - gp.size(), gp.size(), gp) == 0)
                 comp.resize(comp.size() - gp.size());

@@ -2608,6 +2608,11 @@ struct mh_ctx {
     int nmo = 0;
     Lanes lanes_mo{};
     double* d_mo = nullptr;
+    // metabolics goals (kind 18): their count, the muscle entries of all of
+    // them concatenated in goal order, and k_metabolics' lane values
+    // [G][stride][nmet_entries] (the lanes are lanes_mo)
+    int nmet = 0, nmet_entries = 0;
+    double* d_met = nullptr;
     bool use_roles = false;        // MOCOHIP_ROLES=1: k_role (+ k_couple) for the Jacobian lanes
     int role_threads = 256;        // k_role workgroup size (MOCOHIP_ROLE_THREADS: 64..512)
     int iv_threads = 1024;         // k_interval workgroup size, Jacobian lanes (MOCOHIP_IV_THREADS: 256..1024)
@@ -3102,6 +3107,24 @@ struct MuscleOutputsBackend {
     void (*probe)(mh_ctx*, int nout, const int* mus, const int* which, int np, const double* in, double* out);
 };
 const MuscleOutputsBackend* muscle_outputs_backends();
+// The metabolics goals' kernels (metabolics.hip), likewise.  eval: mode 0 / 1
+// as above; probe: mh_eval_metabolics' rows (one component's term block of nm
+// muscles in device arrays, 5 + nm values per row).
+struct MetabolicsBackend {
+    void (*eval)(mh_ctx*, const double* x, int mode);
+    void (*probe)(mh_ctx*, int nm, const int* idx, const int* col, const double* w, int np, const double* in,
+                  double* out);
+};
+const MetabolicsBackend* metabolics_backends();
+// A metabolics term block (include/mocohip.h MH_GOAL_METABOLICS): six header
+// terms, then six per muscle.
+#define MH_MET_HEADER 6
+#define MH_MET_PER_MUSCLE 6
+// The first complaint about the block idx / col / w of n terms on a model of
+// nmuscles muscles into msg ("" when it is well formed); the value is MH_OK
+// or MH_ERR_INVALID.
+int metabolics_block_check(int nmuscles, const int32_t* idx, const int32_t* col, const double* w, int64_t n,
+        char* msg, size_t cap);
 // A model-specialized back end (generated/gen_<model>.hip): the task kernels
 // (default) and the one-lane-per-DAE kernel (MOCOHIP_BACKEND=lane), for the
 // model structure match() accepts (multibody dynamics mode and prescribed

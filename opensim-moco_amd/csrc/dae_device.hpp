@@ -356,15 +356,23 @@ __device__ __forceinline__ void dgf_eval(const DevModel& M, int im, double LMT, 
     (void)fiberWidth;
 }
 
-// One output of a muscle (include/mocohip.h mh_muscle_output `which`) from
-// its muscle-tendon length and lengthening speed and its own inputs:
-// calcMuscleLengthInfoHelper, calcFiberVelocityInfoHelper and
-// calcMuscleDynamicsInfoHelper (DeGrooteFregly2016Muscle.cpp:240-415) in
+// Every quantity the outputs of a muscle are picked from (dgf_output) or
+// built on (the metabolics model, metabolics.hip), from one evaluation.
+struct DgfOut {
+    double LMT, VMT, act, exc;
+    double fiberWidth, fiberLength, nfl, cosPenn, tendonLength, tendonStrain, flat;
+    double fAL, fPE, fiberVelocity, nfv, fvat, tendonVelocity, fV;
+    double activeF, conPass, nonCon, total, passiveF, T;
+};
+
+// The muscle's quantities from its muscle-tendon length and lengthening speed
+// and its own inputs: calcMuscleLengthInfoHelper, calcFiberVelocityInfoHelper
+// and calcMuscleDynamicsInfoHelper (DeGrooteFregly2016Muscle.cpp:240-415) in
 // dgf_eval's expressions (tendon_force is its T to rounding: dgf_eval is
 // compiled with the default contraction), each operation rounded on its own.
 // Not used by the DAE.
-__device__ __forceinline__ double dgf_output(const DevModel& M, int im, int which, double LMT, double VMT,
-        double act, double exc, double ftn, bool compliant, bool implicit_tendon, double dft) {
+__device__ __forceinline__ DgfOut dgf_outputs(const DevModel& M, int im, double LMT, double VMT, double act,
+        double exc, double ftn, bool compliant, bool implicit_tendon, double dft) {
 #pragma clang fp contract(off)
     const mh_muscle& mu = M.mus[im];
     const double* dv = M.mus_derived + (long)im * MUS_DERIVED;
@@ -408,6 +416,21 @@ __device__ __forceinline__ double dgf_output(const DevModel& M, int im, int whic
     const double total = activeF + conPass + nonCon;
     const double passiveF = conPass + nonCon;
     const double T = compliant ? Fmax * ftn : total * cosPenn;
+    return DgfOut{LMT, VMT, act, exc, fiberWidth, fiberLength, nfl, cosPenn, tendonLength, tendonStrain, flat,
+                  fAL, fPE, fiberVelocity, nfv, fvat, tendonVelocity, fV, activeF, conPass, nonCon, total, passiveF, T};
+}
+
+// One output of a muscle (include/mocohip.h mh_muscle_output `which`), picked
+// from dgf_outputs' quantities.
+__device__ __forceinline__ double dgf_output(const DevModel& M, int im, int which, double LMT, double VMT,
+        double act, double exc, double ftn, bool compliant, bool implicit_tendon, double dft) {
+#pragma clang fp contract(off)
+    const DgfOut o = dgf_outputs(M, im, LMT, VMT, act, exc, ftn, compliant, implicit_tendon, dft);
+    const double fiberWidth = o.fiberWidth, fiberLength = o.fiberLength, nfl = o.nfl, cosPenn = o.cosPenn;
+    const double tendonLength = o.tendonLength, tendonStrain = o.tendonStrain, flat = o.flat, fAL = o.fAL, fPE = o.fPE;
+    const double fiberVelocity = o.fiberVelocity, nfv = o.nfv, fvat = o.fvat, tendonVelocity = o.tendonVelocity;
+    const double fV = o.fV, activeF = o.activeF, conPass = o.conPass, nonCon = o.nonCon, total = o.total;
+    const double passiveF = o.passiveF, T = o.T;
     switch (which) {
     case MH_MO_LENGTH: return LMT;
     case MH_MO_LENGTHENING_SPEED: return VMT;

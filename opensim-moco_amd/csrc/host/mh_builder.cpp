@@ -1037,6 +1037,90 @@ void make_rep(const Problem& P, ProblemRep& R) {
                 fail("output path '" + g.output_path + "' is not of the form <component path>|<output>; " + supported);
             std::string comp = g.output_path.substr(0, bar);
             const std::string out = g.output_path.substr(bar + 1);
+            double den = 1.0;
+            if (g.divide_by_mass) {
+                den = 0.0;
+                for (auto& body : model.bodies) den += body.mass;
+            }
+            if (g.has_metabolics && (comp == "/" + g.metabolics.name || comp == "/componentset/" + g.metabolics.name)) {
+                // an output of a Bhargava2004Metabolics (problem.py
+                // parse_metabolics_output_path, model.py term_block): the
+                // component in the goal's terms (MH_GOAL_METABOLICS)
+                const MetabolicsComponent& mc = g.metabolics;
+                const std::string me = "Bhargava2004Metabolics '" + mc.name + "'";
+                if (mc.smoothing_type != "tanh" && mc.smoothing_type != "huber")
+                    fail(me + ": unknown smoothing_type '" + mc.smoothing_type + "' (tanh or huber)");
+                if (!(mc.velocity_smoothing > 0.0) || !(mc.power_smoothing > 0.0) || !(mc.heat_rate_smoothing > 0.0))
+                    fail(me + ": a smoothing value is not positive");
+                if (mc.muscles.empty()) fail(me + ": no muscles");
+                std::vector<int> mus;
+                for (size_t a = 0; a < mc.muscles.size(); ++a) {
+                    const MetabolicsMuscle& mp = mc.muscles[a];
+                    for (size_t b = 0; b < a; ++b)
+                        if (mc.muscles[b].name == mp.name) fail(me + ": muscle name '" + mp.name + "' is used twice");
+                    int im = -1;
+                    for (size_t i = 0; i < model.muscles.size() && im < 0; ++i)
+                        if (mp.muscle_path == model.muscles[i].path || mp.muscle_path == model.muscles[i].name)
+                            im = (int)i;
+                    if (im < 0)
+                        fail(me + ": muscle '" + mp.name + "': no muscle '" + mp.muscle_path + "' in the model");
+                    if (!(mp.ratio_slow_twitch_fibers >= 0.0 && mp.ratio_slow_twitch_fibers <= 1.0))
+                        fail(me + ": muscle '" + mp.name + "': ratio_slow_twitch_fibers is outside [0, 1]");
+                    mus.push_back(im);
+                }
+                static const char* const outputs[MH_MET_COUNT] = {
+                    "total_metabolic_rate", "total_activation_rate", "total_maintenance_rate",
+                    "total_shortening_rate", "total_mechanical_work_rate", "muscle_metabolic_rate"};
+                const size_t colon = out.find(':');
+                const std::string oname = out.substr(0, colon), chan = colon == std::string::npos ? "" : out.substr(colon + 1);
+                int which = -1, channel = -1;
+                for (int k = 0; k < (int)MH_MET_COUNT; ++k)
+                    if (oname == outputs[k]) which = k;
+                if (which < 0 || (which == MH_MET_MUSCLE_METABOLIC_RATE) != (colon != std::string::npos))
+                    fail("output path '" + g.output_path + "': no supported output '" + out +
+                         "' of a Bhargava2004Metabolics");
+                if (which == MH_MET_MUSCLE_METABOLIC_RATE) {
+                    for (size_t a = 0; a < mc.muscles.size() && channel < 0; ++a) {
+                        const Muscle& mu = model.muscles[mus[a]];
+                        if (chan == mc.muscles[a].name || chan == mc.muscles[a].muscle_path || chan == mu.path ||
+                                chan == mu.name)
+                            channel = (int)a;
+                    }
+                    if (channel < 0)
+                        fail("output path '" + g.output_path + "': component '" + comp + "' has no muscle '" + chan + "'");
+                }
+                double total_mass = 0.0;
+                for (auto& body : model.bodies) total_mass += body.mass;
+                const double basal = mc.basal_coefficient * std::pow(total_mass, mc.basal_exponent);
+                const bool smooth = mc.use_smoothing;
+                const int flags = (smooth ? 1 : 0) | (smooth && mc.smoothing_type == "huber" ? 2 : 0) |
+                                  (mc.use_force_dependent_shortening_prop_constant ? 4 : 0) |
+                                  (mc.include_negative_mechanical_work ? 8 : 0) |
+                                  (mc.forbid_negative_total_power ? 16 : 0) |
+                                  (mc.enforce_minimum_heat_rate_per_muscle ? 32 : 0);
+                gs.kind = MH_GOAL_METABOLICS;
+                term(flags, which, den);
+                term(0, channel, basal);
+                term(0, 0, mc.muscle_effort_scaling_factor);
+                term(0, 0, mc.velocity_smoothing);
+                term(0, 0, mc.power_smoothing);
+                term(0, 0, mc.heat_rate_smoothing);
+                for (size_t a = 0; a < mc.muscles.size(); ++a) {
+                    const MetabolicsMuscle& mp = mc.muscles[a];
+                    const Muscle& mu = model.muscles[mus[a]];
+                    const double mass = std::isnan(mp.muscle_mass)
+                            ? (mu.max_isometric_force / mp.specific_tension) * mp.density * mu.optimal_fiber_length
+                            : mp.muscle_mass;
+                    if (!(mass > 0.0)) fail(me + ": muscle '" + mp.name + "': muscle mass is not positive");
+                    term(mus[a], 0, mass);
+                    term(0, 0, mp.ratio_slow_twitch_fibers);
+                    term(0, 0, mp.activation_constant_slow_twitch);
+                    term(0, 0, mp.activation_constant_fast_twitch);
+                    term(0, 0, mp.maintenance_constant_slow_twitch);
+                    term(0, 0, mp.maintenance_constant_fast_twitch);
+                }
+                break;
+            }
             const std::string gp = "/geometrypath";
             const bool path_output = comp.size() >= gp.size() && comp.compare(comp.size() - gp.size(), gp.size(), gp) == 0;
             if (path_output) comp.resize(comp.size() - gp.size());
@@ -1050,11 +1134,6 @@ void make_rep(const Problem& P, ProblemRep& R) {
             const int id = muscle_output_id(out);
             if (id >= 0 && (!path_output || id < 2)) which = id;
             if (which < 0) fail("output path '" + g.output_path + "': no supported output '" + out + "'; " + supported);
-            double den = 1.0;
-            if (g.divide_by_mass) {
-                den = 0.0;
-                for (auto& body : model.bodies) den += body.mass;
-            }
             gs.kind = MH_GOAL_OUTPUT;
             term(im, which, den);
             break;
@@ -1596,6 +1675,34 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
                 g.name = t.s(); g.weight = t.d(); g.output_path = t.s();
                 g.divide_by_mass = t.i() != 0;
                 g.divide_by_displacement = t.i() != 0;
+            } else if (kind == "metabolics") {
+                // an output goal with the Bhargava2004Metabolics component its
+                // path names (describe.py)
+                g.kind = Goal::OUTPUT;
+                g.name = t.s(); g.weight = t.d(); g.output_path = t.s();
+                g.divide_by_mass = t.i() != 0;
+                g.divide_by_displacement = t.i() != 0;
+                g.has_metabolics = true;
+                MetabolicsComponent& mc = g.metabolics;
+                mc.name = t.s();
+                mc.enforce_minimum_heat_rate_per_muscle = t.i() != 0;
+                mc.use_force_dependent_shortening_prop_constant = t.i() != 0;
+                mc.basal_coefficient = t.d(); mc.basal_exponent = t.d(); mc.muscle_effort_scaling_factor = t.d();
+                mc.include_negative_mechanical_work = t.i() != 0;
+                mc.forbid_negative_total_power = t.i() != 0;
+                mc.use_smoothing = t.i() != 0;
+                mc.smoothing_type = t.s();
+                mc.velocity_smoothing = t.d(); mc.power_smoothing = t.d(); mc.heat_rate_smoothing = t.d();
+                const long nm = t.i();
+                for (long k = 0; k < nm; ++k) {
+                    MetabolicsMuscle mp;
+                    mp.name = t.s(); mp.muscle_path = t.s();
+                    mp.ratio_slow_twitch_fibers = t.d(); mp.specific_tension = t.d(); mp.density = t.d();
+                    mp.activation_constant_slow_twitch = t.d(); mp.activation_constant_fast_twitch = t.d();
+                    mp.maintenance_constant_slow_twitch = t.d(); mp.maintenance_constant_fast_twitch = t.d();
+                    mp.muscle_mass = t.d();
+                    mc.muscles.push_back(mp);
+                }
             } else if (kind == "aux_derivatives") {
                 g.kind = Goal::AUX_DERIVATIVES;
                 g.name = t.s(); g.weight = t.d();

@@ -245,6 +245,25 @@ struct VariableInfo {
     Bounds bounds, initial, final_;
 };
 
+// A Bhargava2004Metabolics component (model.py Bhargava2004Metabolics): it
+// travels with the output goal that reads it (a `goal metabolics` record).
+struct MetabolicsMuscle {
+    std::string name, muscle_path;
+    double ratio_slow_twitch_fibers = 0.5, specific_tension = 0.25e6, density = 1059.7;
+    double activation_constant_slow_twitch = 40.0, activation_constant_fast_twitch = 133.0;
+    double maintenance_constant_slow_twitch = 74.0, maintenance_constant_fast_twitch = 111.0;
+    double muscle_mass = std::nan("");   // NaN: Fmax / specific_tension * density * optimal_fiber_length
+};
+struct MetabolicsComponent {
+    std::string name = "metabolics";
+    bool enforce_minimum_heat_rate_per_muscle = true, use_force_dependent_shortening_prop_constant = false;
+    double basal_coefficient = 1.2, basal_exponent = 1.0, muscle_effort_scaling_factor = 1.0;
+    bool include_negative_mechanical_work = true, forbid_negative_total_power = true, use_smoothing = false;
+    std::string smoothing_type = "tanh";
+    double velocity_smoothing = 10.0, power_smoothing = 10.0, heat_rate_smoothing = 10.0;
+    std::vector<MetabolicsMuscle> muscles;
+};
+
 struct Goal {
     enum Kind { CONTROL, STATE_TRACKING, FINAL_TIME, SUM_SQUARED_STATE, INITIAL_ACTIVATION, MARKER_FINAL,
                 AUX_DERIVATIVES, MARKER_TRACKING, TRANSLATION_TRACKING, ORIENTATION_TRACKING,
@@ -276,6 +295,10 @@ struct Goal {
     // output goal (problem.py MocoOutputGoal)
     std::string output_path;
     bool divide_by_mass = false, divide_by_displacement = false;
+    // the metabolics component output_path names, when it names one
+    // (MH_GOAL_METABOLICS); otherwise the path is a muscle's
+    bool has_metabolics = false;
+    MetabolicsComponent metabolics;
 };
 
 // Bound function of MocoControlBoundConstraint: OpenSim::Constant,

@@ -1692,6 +1692,41 @@ static void shard_quadrature(mh_ctx* c) {
     }
 }
 
+int metabolics_block_check(int nmuscles, const int32_t* idx, const int32_t* col, const double* w, int64_t n,
+        char* msg, size_t cap) {
+    msg[0] = 0;
+    auto bad = [&](const char* fmt, auto... a) {
+        snprintf(msg, cap, fmt, a...);
+        return (int)MH_ERR_INVALID;
+    };
+    if (n < MH_MET_HEADER + MH_MET_PER_MUSCLE || (n - MH_MET_HEADER) % MH_MET_PER_MUSCLE != 0)
+        return bad("%lld terms are not six header terms and six per muscle", (long long)n);
+    const int nm = (int)((n - MH_MET_HEADER) / MH_MET_PER_MUSCLE);
+    if (idx[0] < 0 || idx[0] >= 64 || ((idx[0] & 2) && !(idx[0] & 1))) return bad("bad option flags %d", idx[0]);
+    if (col[0] < 0 || col[0] >= MH_MET_COUNT) return bad("output %d out of range", col[0]);
+    if (col[0] == MH_MET_MUSCLE_METABOLIC_RATE ? (col[1] < 0 || col[1] >= nm) : col[1] != -1)
+        return bad("channel %d does not fit output %d of %d muscles", col[1], col[0], nm);
+    for (int64_t k = 0; k < n; ++k) {
+        const bool first = k >= MH_MET_HEADER && (k - MH_MET_HEADER) % MH_MET_PER_MUSCLE == 0;
+        if ((k != 0 && !first && idx[k] != 0) || (k > 1 && col[k] != 0))
+            return bad("term %lld: an unused index or column is not 0", (long long)k);
+    }
+    if (!(w[0] > 0.0) || !std::isfinite(w[0])) return bad("divisor %g is not positive and finite", w[0]);
+    if (!std::isfinite(w[1])) return bad("basal rate %g is not finite", w[1]);
+    if (!std::isfinite(w[2])) return bad("muscle effort scaling factor %g is not finite", w[2]);
+    for (int k = 3; k < 6; ++k)
+        if (!(w[k] > 0.0) || !std::isfinite(w[k])) return bad("smoothing %g is not positive and finite", w[k]);
+    for (int m = 0; m < nm; ++m) {
+        const int mb = MH_MET_HEADER + MH_MET_PER_MUSCLE * m;
+        if (idx[mb] < 0 || idx[mb] >= nmuscles) return bad("muscle %d out of range", idx[mb]);
+        if (!(w[mb] > 0.0) || !std::isfinite(w[mb])) return bad("muscle mass %g is not positive and finite", w[mb]);
+        if (!(w[mb + 1] >= 0.0 && w[mb + 1] <= 1.0)) return bad("slow-twitch ratio %g is outside [0, 1]", w[mb + 1]);
+        for (int k = 2; k < 6; ++k)
+            if (!std::isfinite(w[mb + k])) return bad("heat constant %g is not finite", w[mb + k]);
+    }
+    return MH_OK;
+}
+
 static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options* o,
         std::vector<int>& coord_body, std::vector<int>& act_state, std::vector<int>& ftn_state,
         std::vector<int>& mus_control, double& tau_act, double& tau_deact) {
@@ -2006,6 +2041,19 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
             if (!(den > 0.0) || !std::isfinite(den))
                 return set_err(MH_ERR_INVALID, "goal %d: output goal: divisor %g is not positive and finite", g,
                                den);
+            continue;
+        }
+        if (G.kind == MH_GOAL_METABOLICS) {
+            // six header terms, then six per muscle (include/mocohip.h)
+            if (G.term_begin < 0 || G.term_count < 0 || (int64_t)G.term_begin + G.term_count > p->nterms)
+                return set_err(MH_ERR_INVALID, "goal %d: metabolics goal: bad terms", g);
+            if (p->nparameters > 0)
+                return set_err(MH_ERR_UNSUPPORTED, "goal %d: metabolics goal with MocoParameters", g);
+            char msg[200];
+            const int tb = G.term_begin;
+            if (metabolics_block_check(M.nmuscles, p->goal_index + tb, p->goal_column + tb, p->goal_weight + tb,
+                                       G.term_count, msg, sizeof msg) != MH_OK)
+                return set_err(MH_ERR_INVALID, "goal %d: metabolics goal: %s", g, msg);
             continue;
         }
         if (G.kind < MH_GOAL_CONTROL || (G.kind > MH_GOAL_MARKER_FINAL && !tracking))
@@ -2600,6 +2648,16 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     for (const mh_goal& G : c->goals) c->nmo += G.kind == MH_GOAL_OUTPUT;
     c->lanes_mo = c->lanes_jr;
     const size_t o_mo = c->nmo ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_mo.stride * c->nmo) : 0;
+    // metabolics goals: k_metabolics' lane values, one per muscle entry, on
+    // the same lanes
+    c->nmet = c->nmet_entries = 0;
+    for (const mh_goal& G : c->goals)
+        if (G.kind == MH_GOAL_METABOLICS) {
+            ++c->nmet;
+            c->nmet_entries += (G.term_count - MH_MET_HEADER) / MH_MET_PER_MUSCLE;
+        }
+    const size_t o_met =
+            c->nmet ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_mo.stride * c->nmet_entries) : 0;
     const size_t o_f = A.reserve(sizeof(double) * 4);
     const size_t o_epc = A.reserve(sizeof(double) * (size_t)std::max(1, c->ngoals));   // endpoint costs
     const int npts_iv = c->scheme == MH_HERMITE_SIMPSON ? 3 : 2;
@@ -2805,6 +2863,7 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
         c->d_at_live = (const int*)(b + o_atlive);
     }
     if (c->nmo) c->d_mo = (double*)(b + o_mo);
+    if (c->nmet) c->d_met = (double*)(b + o_met);
     c->has_marker = false;
     for (int g = 0; g < p->ngoals; ++g) c->has_marker |= p->goals[g].kind == MH_GOAL_MARKER_FINAL;
     if (MT.nm > 0) MT.tab = (const int*)(b + o_mttab);
@@ -3847,6 +3906,12 @@ static void launch_muscle_outputs(mh_ctx* c, int mode) {
     muscle_outputs_backends()[c->size_class].eval(c, c->d_x, mode);
 }
 
+// The metabolics goals' likewise, after the muscle-output goals'.
+static void launch_metabolics(mh_ctx* c, int mode) {
+    if (c->nmet == 0) return;
+    metabolics_backends()[c->size_class].eval(c, c->d_x, mode);
+}
+
 // The objective (partial = false) or this shard's partial of it (partial =
 // true: the integrals over the shard's own mesh intervals, d_quadp, and the
 // endpoint goals -- final time, final marker -- on the shard that owns the
@@ -3868,6 +3933,7 @@ static int eval_f_impl(mh_ctx* c, const double* x, double* f, bool partial) {
     launch_joint_reaction(c, 0);       // and the joint-reaction goals'
     launch_accel_tracking(c, 0);       // and the acceleration-tracking goals'
     launch_muscle_outputs(c, 0);       // and the muscle-output goals'
+    launch_metabolics(c, 0);           // and the metabolics goals'
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)
@@ -3904,6 +3970,7 @@ static int eval_grad_f_impl(mh_ctx* c, const double* x, double* grad, bool parti
     launch_joint_reaction(c, 1);       // after both: adds to every direction's entry
     launch_accel_tracking(c, 1);       // after the three: adds to its live directions' entries
     launch_muscle_outputs(c, 1);       // after the four: adds to the entries of the inputs an output reads
+    launch_metabolics(c, 1);           // after the five: adds to the entries of the inputs its muscles read
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)   // after k_grad: adds to the final coordinates' entries
@@ -3944,6 +4011,7 @@ extern "C" int mh_eval_objective_terms(mh_ctx* c, const double* x, double* terms
     launch_joint_reaction(c, 0);
     launch_accel_tracking(c, 0);
     launch_muscle_outputs(c, 0);
+    launch_metabolics(c, 0);
     HIPCHK(hipGetLastError());
     if (c->has_marker)
         hipLaunchKernelGGL(k_marker_final, dim3((unsigned)c->ngoals), dim3(128), 0, c->stream, c->M, L, c->GS,
@@ -4055,6 +4123,39 @@ extern "C" int mh_eval_muscle_outputs(mh_ctx* c, int32_t nout, const int32_t* mu
     HIPCHK(hipStreamSynchronize(c->stream));
     (void)hipFree(din);
     (void)hipFree(dout);
+    (void)hipFree(dsel);
+    return MH_OK;
+}
+
+extern "C" int mh_eval_metabolics(mh_ctx* c, int32_t nterms, const int32_t* index, const int32_t* column,
+        const double* weight, int32_t np, const double* inputs, double* out) {
+    if (!c || !index || !column || !weight || !inputs || !out) return set_err(MH_ERR_INVALID, "bad argument");
+    if (np <= 0) return set_err(MH_ERR_INVALID, "mh_eval_metabolics: %d rows", np);
+    if (c->NPAR > 0) return set_err(MH_ERR_UNSUPPORTED, "mh_eval_metabolics with MocoParameters");
+    char msg[200];
+    if (nterms < 0 || metabolics_block_check(c->M.nmus, index, column, weight, nterms, msg, sizeof msg) != MH_OK)
+        return set_err(MH_ERR_INVALID, "mh_eval_metabolics: %s", nterms < 0 ? "negative term count" : msg);
+    const int nm = (nterms - MH_MET_HEADER) / MH_MET_PER_MUSCLE;
+    HIPCHK(hipSetDevice(c->device));
+    double *din = nullptr, *dout = nullptr, *dw = nullptr;
+    int* dsel = nullptr;
+    const size_t nin = (size_t)np * (1 + c->NI), no = (size_t)np * (5 + nm);
+    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
+    HIPCHK(hipMalloc(&dout, sizeof(double) * no));
+    HIPCHK(hipMalloc(&dw, sizeof(double) * (size_t)nterms));
+    HIPCHK(hipMalloc(&dsel, sizeof(int) * 2 * (size_t)nterms));
+    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dw, weight, sizeof(double) * nterms, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dsel, index, sizeof(int) * nterms, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(dsel + nterms, column, sizeof(int) * nterms, hipMemcpyHostToDevice, c->stream));
+    (void)hipGetLastError();
+    metabolics_backends()[c->size_class].probe(c, nm, dsel, dsel + nterms, dw, np, din, dout);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * no, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    (void)hipFree(dw);
     (void)hipFree(dsel);
     return MH_OK;
 }

@@ -38,6 +38,12 @@ MUSCLE_OUTPUTS = (
     "passive_fiber_damping_force_along_tendon", "fiber_active_power", "fiber_passive_power", "tendon_power",
     "muscle_power")
 MH_MO_COUNT = len(MUSCLE_OUTPUTS)
+MH_GOAL_METABOLICS = 18
+# enum mh_metabolics_output: the outputs of a Bhargava2004Metabolics, by id
+# (the last is the list output: "muscle_metabolic_rate:<channel>")
+METABOLICS_OUTPUTS = ("total_metabolic_rate", "total_activation_rate", "total_maintenance_rate",
+                      "total_shortening_rate", "total_mechanical_work_rate", "muscle_metabolic_rate")
+MH_MET_COUNT = len(METABOLICS_OUTPUTS)
 MH_HERMITE_SIMPSON, MH_TRAPEZOIDAL = 0, 1
 MH_DYNAMICS_EXPLICIT, MH_DYNAMICS_IMPLICIT = 0, 1
 MH_FD_CENTRAL, MH_FD_FORWARD, MH_FD_BACKWARD = 0, 1, 2
@@ -265,6 +271,7 @@ MOCOHIP_SYMBOLS = {
     "mh_eval_joint_reaction": (i32, [C.c_void_p, i32, i32, P(f64), P(f64)]),
     "mh_eval_frame_accelerations": (i32, [C.c_void_p, i32, i32, P(f64), P(f64)]),
     "mh_eval_muscle_outputs": (i32, [C.c_void_p, i32, P(i32), P(i32), i32, P(f64), P(f64)]),
+    "mh_eval_metabolics": (i32, [C.c_void_p, i32, P(i32), P(i32), P(f64), i32, P(f64), P(f64)]),
     "mh_eval_path": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
     "mh_set_timing": (i32, [C.c_void_p, i32]),
     "mh_get_backend_flags": (i32, [C.c_void_p, C.c_char_p, i32]),

@@ -1366,3 +1366,43 @@ def gait10dof18musc_muscle_outputs(num_mesh_intervals: int = 200, output: str = 
         st.problem.goals.insert(len(st.problem.goals) - 1,
                                 MocoOutputGoal(f"{output}_{mu.name}", weight, output_path=f"{mu.path}|{output}"))
     return st
+
+
+# ---- MocoOutputGoal over a Bhargava2004Metabolics component -------------------
+def hanging_muscle_metabolics(num_mesh_intervals: int = 5, output: str = "total_metabolic_rate",
+                              divide_by_mass: bool = False, weight: float = 1.0, muscle_mass: float = float("nan"),
+                              ratio_slow_twitch_fibers: float = 0.5, **kw) -> MocoStudy:
+    """hanging_muscle with a Bhargava2004Metabolics component "metabolics" over
+    its muscle and one MocoOutputGoal "met" on ``/metabolics|<output>`` as the
+    only goal.  Keywords that are properties of the component
+    (use_smoothing, smoothing_type, include_negative_mechanical_work, ...) go
+    to it, the others to hanging_muscle."""
+    from .model import Bhargava2004Metabolics
+    own = {k: kw.pop(k) for k in list(kw) if k in Bhargava2004Metabolics.__dataclass_fields__}
+    st = hanging_muscle(num_mesh_intervals, **kw)
+    met = Bhargava2004Metabolics("metabolics", **own)
+    met.add_muscle("actuator", "/forceset/actuator", ratio_slow_twitch_fibers=ratio_slow_twitch_fibers,
+                   muscle_mass=muscle_mass)
+    st.problem.model.add_component(met)
+    st.problem.goals = [MocoOutputGoal("met", weight, output_path="/metabolics|" + output,
+                                       divide_by_mass=divide_by_mass)]
+    return st
+
+
+def gait10dof18musc_metabolics(num_mesh_intervals: int = 200, smoothing: str = "tanh", weight: float = 0.1,
+                               **kw) -> MocoStudy:
+    """gait10dof18musc's study with a Bhargava2004Metabolics component
+    "metabolics" over all 18 muscles (use_smoothing, ``smoothing`` = "tanh" or
+    "huber") and a MocoOutputGoal "met" on its total metabolic rate divided by
+    the model's mass, before the effort goal, as example2DWalkingMetabolics
+    sets its metabolic cost up."""
+    from .model import Bhargava2004Metabolics
+    st = gait10dof18musc(num_mesh_intervals, **kw)
+    met = Bhargava2004Metabolics("metabolics", use_smoothing=True, smoothing_type=smoothing)
+    for mu in st.problem.model.muscles:
+        met.add_muscle(mu.name, mu.path)
+    st.problem.model.add_component(met)
+    st.problem.goals.insert(len(st.problem.goals) - 1,
+                            MocoOutputGoal("met", weight, output_path="/metabolics|total_metabolic_rate",
+                                           divide_by_mass=True))
+    return st

@@ -192,6 +192,24 @@ def describe(study) -> str:
                                  _s(g.loads_frame), _s(g.expressed_in_frame_path), str(len(g.reaction_measures))]
                                 + [_s(m) for m in g.reaction_measures] + [str(len(w))]
                                 + [f"{_s(k)} {_d(v)}" for k, v in w]))
+        elif isinstance(g, MocoOutputGoal) and m.find_component(g.output_path.partition("|")[0]) is not None:
+            # the Bhargava2004Metabolics component the path names travels with
+            # the goal: its properties, then its muscles' parameters
+            c = m.find_component(g.output_path.partition("|")[0])
+            rec = ["goal", "metabolics", _s(g.name), _d(g.weight), _s(g.output_path),
+                   str(int(bool(g.divide_by_mass))), str(int(bool(g.divide_by_displacement))), _s(c.name),
+                   str(int(bool(c.enforce_minimum_heat_rate_per_muscle))),
+                   str(int(bool(c.use_force_dependent_shortening_prop_constant))), _d(c.basal_coefficient),
+                   _d(c.basal_exponent), _d(c.muscle_effort_scaling_factor),
+                   str(int(bool(c.include_negative_mechanical_work))), str(int(bool(c.forbid_negative_total_power))),
+                   str(int(bool(c.use_smoothing))), _s(c.smoothing_type), _d(c.velocity_smoothing),
+                   _d(c.power_smoothing), _d(c.heat_rate_smoothing), str(len(c.muscles))]
+            for mp in c.muscles:
+                rec += [_s(mp.name), _s(mp.muscle_path), _d(mp.ratio_slow_twitch_fibers), _d(mp.specific_tension),
+                        _d(mp.density), _d(mp.activation_constant_slow_twitch), _d(mp.activation_constant_fast_twitch),
+                        _d(mp.maintenance_constant_slow_twitch), _d(mp.maintenance_constant_fast_twitch),
+                        _d(mp.muscle_mass)]
+            out.append(" ".join(rec))
         elif isinstance(g, MocoOutputGoal):
             out.append(" ".join(["goal", "output", _s(g.name), _d(g.weight), _s(g.output_path),
                                  str(int(bool(g.divide_by_mass))), str(int(bool(g.divide_by_displacement)))]))

@@ -338,8 +338,143 @@ class CoordinateCouplerConstraint:
     scale_factor: float = 1.0
 
 
+@dataclass
+class Bhargava2004MetabolicsMuscleParameters:
+    """Bhargava2004Metabolics_MuscleParameters (Bhargava2004Metabolics.cpp:
+    40-70): one muscle of a metabolics component.  ``muscle_mass`` NaN: the
+    mass is Fmax / specific_tension * density * optimal_fiber_length."""
+    name: str
+    muscle_path: str
+    ratio_slow_twitch_fibers: float = 0.5
+    specific_tension: float = 0.25e6
+    density: float = 1059.7
+    activation_constant_slow_twitch: float = 40.0
+    activation_constant_fast_twitch: float = 133.0
+    maintenance_constant_slow_twitch: float = 74.0
+    maintenance_constant_fast_twitch: float = 111.0
+    muscle_mass: float = math.nan
+
+    def mass(self, muscle: "DeGrooteFregly2016Muscle") -> float:
+        if not math.isnan(self.muscle_mass):
+            return float(self.muscle_mass)
+        return (float(muscle.max_isometric_force) / float(self.specific_tension)) * float(self.density) \
+            * float(muscle.optimal_fiber_length)
+
+
+@dataclass
+class Bhargava2004Metabolics:
+    """Bhargava2004Metabolics (Moco/Moco/Components/Bhargava2004Metabolics.
+    {h,cpp}; properties and defaults of its constructProperties): the metabolic
+    rate of a set of muscles, the sum of each muscle's activation, maintenance
+    and shortening heat rates and mechanical work rate, plus a basal rate for
+    the whole model (include/mocohip.h MH_GOAL_METABOLICS gives the formulas).
+    A component of a Model (Model.add_component), path ``/<name>``; its outputs
+    (abi.METABOLICS_OUTPUTS) are read by MocoOutputGoal and MocoStudy.analyze."""
+    name: str = "metabolics"
+    enforce_minimum_heat_rate_per_muscle: bool = True
+    use_force_dependent_shortening_prop_constant: bool = False
+    basal_coefficient: float = 1.2
+    basal_exponent: float = 1.0
+    muscle_effort_scaling_factor: float = 1.0
+    include_negative_mechanical_work: bool = True
+    forbid_negative_total_power: bool = True
+    use_smoothing: bool = False
+    smoothing_type: str = "tanh"
+    velocity_smoothing: float = 10.0
+    power_smoothing: float = 10.0
+    heat_rate_smoothing: float = 10.0
+    muscles: List[Bhargava2004MetabolicsMuscleParameters] = field(default_factory=list)
+
+    @property
+    def path(self) -> str:
+        return "/" + self.name
+
+    def add_muscle(self, name: str, muscle_path: str, ratio_slow_twitch_fibers: float = 0.5,
+                   specific_tension: float = 0.25e6, density: float = 1059.7,
+                   activation_constant_slow_twitch: float = 40.0, activation_constant_fast_twitch: float = 133.0,
+                   maintenance_constant_slow_twitch: float = 74.0, maintenance_constant_fast_twitch: float = 111.0,
+                   muscle_mass: float = math.nan):
+        """Bhargava2004Metabolics::addMuscle: ``muscle_path`` is the path (or
+        the name) of a DeGrooteFregly2016Muscle of the model."""
+        mp = Bhargava2004MetabolicsMuscleParameters(
+            name, muscle_path, ratio_slow_twitch_fibers, specific_tension, density, activation_constant_slow_twitch,
+            activation_constant_fast_twitch, maintenance_constant_slow_twitch, maintenance_constant_fast_twitch,
+            muscle_mass)
+        self.muscles.append(mp)
+        return mp
+
+    def muscle_index(self, model: "Model", mp: Bhargava2004MetabolicsMuscleParameters) -> int:
+        """The model's muscle that ``mp`` names; ValueError for a path that
+        names none, or an actuator that is no DeGrooteFregly2016Muscle."""
+        for i, mu in enumerate(model.muscles):
+            if mp.muscle_path in (mu.path, mu.name):
+                return i
+        other = next((a for a in model.actuators if mp.muscle_path in (getattr(a, "path", None), a.name)), None)
+        if other is not None:
+            raise ValueError(f"Bhargava2004Metabolics '{self.name}': muscle '{mp.name}': '{mp.muscle_path}' is a "
+                             f"{type(other).__name__}, not a DeGrooteFregly2016Muscle")
+        raise ValueError(f"Bhargava2004Metabolics '{self.name}': muscle '{mp.name}': no muscle '{mp.muscle_path}' "
+                         "in the model")
+
+    def check(self, model: "Model"):
+        """ValueError naming the offender: an unknown muscle path, a muscle
+        that is no DeGrooteFregly2016Muscle, a name used twice, a ratio outside
+        [0, 1], a mass <= 0, a smoothing value <= 0, an unknown smoothing
+        type."""
+        me = f"Bhargava2004Metabolics '{self.name}'"
+        if self.smoothing_type not in ("tanh", "huber"):
+            raise ValueError(f"{me}: unknown smoothing_type '{self.smoothing_type}' (tanh or huber)")
+        for prop in ("velocity_smoothing", "power_smoothing", "heat_rate_smoothing"):
+            if not float(getattr(self, prop)) > 0.0:
+                raise ValueError(f"{me}: {prop} = {getattr(self, prop)} is not positive")
+        if not self.muscles:
+            raise ValueError(f"{me}: no muscles")
+        seen = set()
+        for mp in self.muscles:
+            if mp.name in seen:
+                raise ValueError(f"{me}: muscle name '{mp.name}' is used twice")
+            seen.add(mp.name)
+            im = self.muscle_index(model, mp)
+            if not 0.0 <= float(mp.ratio_slow_twitch_fibers) <= 1.0:
+                raise ValueError(f"{me}: muscle '{mp.name}': ratio_slow_twitch_fibers = "
+                                 f"{mp.ratio_slow_twitch_fibers} is outside [0, 1]")
+            if not mp.mass(model.muscles[im]) > 0.0:
+                raise ValueError(f"{me}: muscle '{mp.name}': muscle mass {mp.mass(model.muscles[im])} is not positive")
+
+    def flags(self) -> int:
+        """The option flags of include/mocohip.h MH_GOAL_METABOLICS."""
+        return ((1 if self.use_smoothing else 0) | (2 if self.use_smoothing and self.smoothing_type == "huber" else 0)
+                | (4 if self.use_force_dependent_shortening_prop_constant else 0)
+                | (8 if self.include_negative_mechanical_work else 0)
+                | (16 if self.forbid_negative_total_power else 0)
+                | (32 if self.enforce_minimum_heat_rate_per_muscle else 0))
+
+    def term_block(self, model: "Model", output: int = 0, channel: int = -1, divisor: float = 1.0):
+        """(index, column, weight) lists: the component as a goal of kind
+        MH_GOAL_METABOLICS carries it (include/mocohip.h), the muscle masses and
+        the basal rate formed here."""
+        self.check(model)
+        total_mass = 0.0
+        for body in model.bodies.values():
+            total_mass += float(body.mass)
+        basal = float(self.basal_coefficient) * total_mass ** float(self.basal_exponent)
+        idx = [self.flags(), 0, 0, 0, 0, 0]
+        col = [int(output), int(channel), 0, 0, 0, 0]
+        w = [float(divisor), basal, float(self.muscle_effort_scaling_factor), float(self.velocity_smoothing),
+             float(self.power_smoothing), float(self.heat_rate_smoothing)]
+        for mp in self.muscles:
+            im = self.muscle_index(model, mp)
+            idx += [im, 0, 0, 0, 0, 0]
+            col += [0] * 6
+            w += [mp.mass(model.muscles[im]), float(mp.ratio_slow_twitch_fibers),
+                  float(mp.activation_constant_slow_twitch), float(mp.activation_constant_fast_twitch),
+                  float(mp.maintenance_constant_slow_twitch), float(mp.maintenance_constant_fast_twitch)]
+        return idx, col, w
+
+
 class Model:
     def __init__(self, name: str = "model", gravity=(0, -9.80665, 0)):
+        self.components: List[Bhargava2004Metabolics] = []
         self.name = name
         self.gravity = tuple(float(g) for g in gravity)
         self.bodies: Dict[str, Body] = {}
@@ -400,6 +535,24 @@ class Model:
     def add_wrap(self, w: WrapCylinder):
         self.wraps[w.name] = w
         return w
+
+    def add_component(self, component: "Bhargava2004Metabolics"):
+        """Model::addComponent for a Bhargava2004Metabolics: its path is
+        ``/<name>`` (``/componentset/<name>`` is accepted too).  The muscles it
+        names must be in the model already."""
+        if any(c.name == component.name for c in self.components):
+            raise ValueError(f"component name '{component.name}' is used twice")
+        component.check(self)
+        self.components.append(component)
+        return component
+
+    def find_component(self, path: str):
+        """The component with path ``/<name>`` or ``/componentset/<name>``
+        (None: there is none)."""
+        for c in self.components:
+            if path in (c.path, "/componentset/" + c.name):
+                return c
+        return None
 
     def replace_joints_with_welds(self, names: Sequence[str]):
         """ModOpReplaceJointsWithWelds (ModelFactory::replaceJointWithWeldJoint,

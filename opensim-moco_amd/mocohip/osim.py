@@ -346,7 +346,40 @@ def read_osim(path: str, remove_muscles: bool = False,
                     _float(f, "max_control", math.inf)))
             else:
                 raise NotImplementedError(f"force {f.tag} not supported on the hot path")
+    # the metabolics components of <components> (a model's own list) and of
+    # a ComponentSet; other components there are not read, as before
+    for holder in ("components", "ComponentSet/objects"):
+        el = mel.find(holder)
+        for comp in (list(el) if el is not None else []):
+            if comp.tag == "Bhargava2004Metabolics":
+                model.add_component(_metabolics(comp))
     return model
+
+
+def _metabolics(el):
+    """A <Bhargava2004Metabolics> element with its
+    <Bhargava2004Metabolics_MuscleParameters> list: properties that are absent
+    keep the reference's defaults; a muscle's socket_muscle is its path, and
+    provided_muscle_mass counts only with use_provided_muscle_mass."""
+    from .model import Bhargava2004Metabolics
+    d = Bhargava2004Metabolics(el.get("name") or "metabolics")
+    for prop in ("enforce_minimum_heat_rate_per_muscle", "use_force_dependent_shortening_prop_constant",
+                 "include_negative_mechanical_work", "forbid_negative_total_power", "use_smoothing"):
+        setattr(d, prop, _bool(el, prop, getattr(d, prop)))
+    for prop in ("basal_coefficient", "basal_exponent", "muscle_effort_scaling_factor", "velocity_smoothing",
+                 "power_smoothing", "heat_rate_smoothing"):
+        setattr(d, prop, _float(el, prop, getattr(d, prop)))
+    d.smoothing_type = (_text(el, "smoothing_type", d.smoothing_type) or "").strip()
+    for mp in el.findall("muscle_parameters/Bhargava2004Metabolics_MuscleParameters"):
+        provided = _bool(mp, "use_provided_muscle_mass", False)
+        d.add_muscle(mp.get("name"), (_text(mp, "socket_muscle") or "").strip(),
+                     _float(mp, "ratio_slow_twitch_fibers", 0.5), _float(mp, "specific_tension", 0.25e6),
+                     _float(mp, "density", 1059.7), _float(mp, "activation_constant_slow_twitch", 40.0),
+                     _float(mp, "activation_constant_fast_twitch", 133.0),
+                     _float(mp, "maintenance_constant_slow_twitch", 74.0),
+                     _float(mp, "maintenance_constant_fast_twitch", 111.0),
+                     _float(mp, "provided_muscle_mass", math.nan) if provided else math.nan)
+    return d
 
 
 def add_reserves(model: Model, optimal_force: float, bound: float = float("nan")):

@@ -497,14 +497,43 @@ def parse_muscle_output_path(model, output_path: str):
     return im, abi.MUSCLE_OUTPUTS.index(out)
 
 
+def parse_metabolics_output_path(model, output_path: str):
+    """(component, output id, channel) of an output path ``/<component>|
+    <output>`` of a Bhargava2004Metabolics component of the model
+    (abi.METABOLICS_OUTPUTS, include/mocohip.h enum mh_metabolics_output; the
+    list output as ``muscle_metabolic_rate:<muscle name or path>``, its channel
+    the muscle's position in the component, -1 for every other output).  None
+    when the path's component is no metabolics component of the model;
+    ValueError for an output or a channel the component does not have."""
+    comp, sep, out = output_path.partition("|")
+    c = model.find_component(comp) if sep and out else None
+    if c is None:
+        return None
+    supported = ("supported: " + ", ".join(abi.METABOLICS_OUTPUTS[:-1]) + " and " + abi.METABOLICS_OUTPUTS[-1]
+                 + ":<muscle name or path>")
+    name, colon, chan = out.partition(":")
+    if name not in abi.METABOLICS_OUTPUTS or (name == abi.METABOLICS_OUTPUTS[-1]) != bool(colon):
+        raise ValueError(f"output path '{output_path}': no supported output '{out}' of a Bhargava2004Metabolics; "
+                         f"{supported}")
+    if not colon:
+        return c, abi.METABOLICS_OUTPUTS.index(name), -1
+    for pos, mp in enumerate(c.muscles):
+        mu = model.muscles[c.muscle_index(model, mp)]
+        if chan in (mp.name, mp.muscle_path, mu.path, mu.name):
+            return c, abi.MH_MET_COUNT - 1, pos
+    raise ValueError(f"output path '{output_path}': component '{comp}' has no muscle '{chan}'")
+
+
 @dataclass
 class MocoOutputGoal:
     """MocoOutputGoal (Moco/Moco/MocoGoal/MocoOutputGoal.{h,cpp}): the integral
     over the phase of one scalar model output, times the weight, divided by the
     model's total mass with ``divide_by_mass`` (include/mocohip.h
     MH_GOAL_OUTPUT).  ``output_path``: an output of a DeGrooteFregly2016Muscle
-    (parse_muscle_output_path), e.g. "/forceset/soleus_r|tendon_force"; outputs
-    of other components are a follow-up.  ``divide_by_displacement`` needs the
+    (parse_muscle_output_path), e.g. "/forceset/soleus_r|tendon_force", or of a
+    Bhargava2004Metabolics component (parse_metabolics_output_path, include/
+    mocohip.h MH_GOAL_METABOLICS), e.g. "/metabolics|total_metabolic_rate";
+    outputs of other components are a follow-up.  ``divide_by_displacement`` needs the
     reference's calcSystemDisplacement (the displacement of the whole system's
     mass center between the initial and the final state), which is not
     available: NotImplementedError, a follow-up."""
@@ -903,14 +932,22 @@ class ProblemRep:
                 if problem.parameters:
                     raise NotImplementedError("MocoOutputGoal with MocoParameters "
                                               "(the goals' gradient along a parameter is defined as 0)")
-                im, which = parse_muscle_output_path(model, g.output_path)
                 den = 1.0
                 if g.divide_by_mass:
                     den = 0.0
                     for body in model.bodies.values():
                         den += float(body.mass)
-                gs.kind = abi.MH_GOAL_OUTPUT
-                gidx.append(im); gcol.append(which); gw.append(den)
+                met = parse_metabolics_output_path(model, g.output_path)
+                if met is not None:
+                    # an output of a Bhargava2004Metabolics: the component
+                    # travels in the goal's terms (MH_GOAL_METABOLICS)
+                    gs.kind = abi.MH_GOAL_METABOLICS
+                    bi, bc, bw = met[0].term_block(model, met[1], met[2], den)
+                    gidx.extend(bi); gcol.extend(bc); gw.extend(bw)
+                else:
+                    im, which = parse_muscle_output_path(model, g.output_path)
+                    gs.kind = abi.MH_GOAL_OUTPUT
+                    gidx.append(im); gcol.append(which); gw.append(den)
             elif isinstance(g, ImplicitAuxiliaryDerivativesTerm):
                 gs.kind = abi.MH_GOAL_AUX_DERIVATIVES
                 naux = sum(1 for m in model.muscles if not m.ignore_tendon_compliance

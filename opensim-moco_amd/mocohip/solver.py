@@ -682,7 +682,41 @@ class HipNLP(_NLPBase):
             sel = [parse_muscle_output_path(model, c) for c in labels]
             vals = self.eval_muscle_outputs([s[0] for s in sel], [s[1] for s in sel],
                                             np.column_stack([t, self.point_inputs(x)]))
+        # the outputs of the model's Bhargava2004Metabolics components, after
+        # the muscles' columns: "/<component>|total_..." and one
+        # "|muscle_metabolic_rate:<muscle path>" per muscle
+        for comp in getattr(model, "components", []):
+            own = [f"{comp.path}|{o}" for o in abi.METABOLICS_OUTPUTS[:-1]]
+            own += [f"{comp.path}|{abi.METABOLICS_OUTPUTS[-1]}:{model.muscles[comp.muscle_index(model, mp)].path}"
+                    for mp in comp.muscles]
+            keep = [i for i, c in enumerate(own) if any(p.fullmatch(c) for p in pats)]
+            if keep:
+                got = self.eval_metabolics(comp, np.column_stack([t, self.point_inputs(x)]))
+                labels += [own[i] for i in keep]
+                vals = np.column_stack([vals, got[:, keep]])
         return (t, labels, vals) if with_times else (labels, vals)
+
+    def eval_metabolics(self, component, inputs: np.ndarray) -> np.ndarray:
+        """Rows [t, point inputs] (as eval_dae) -> [rows, 5 + muscles]: the
+        Bhargava2004Metabolics ``component`` at every row: total metabolic rate
+        (with the basal rate), total activation, maintenance, shortening and
+        mechanical work rates, then each muscle's metabolic rate
+        (mh_eval_metabolics).  Not tied to a goal."""
+        return self.eval_metabolics_block(*component.term_block(self.rep.problem.model), inputs)
+
+    def eval_metabolics_block(self, index, column, weight, inputs: np.ndarray) -> np.ndarray:
+        """eval_metabolics for a component given as its term block
+        (include/mocohip.h MH_GOAL_METABOLICS; model.py term_block)."""
+        inputs = np.ascontiguousarray(inputs, float)
+        assert inputs.ndim == 2 and inputs.shape[1] == 1 + self.NI
+        idx, col, w = (np.ascontiguousarray(index, np.int32), np.ascontiguousarray(column, np.int32),
+                       np.ascontiguousarray(weight, float))
+        assert len(idx) == len(col) == len(w)
+        npts, ncol = inputs.shape[0], 5 + max(0, (len(idx) - 6) // 6)
+        out = np.empty((max(npts, 1), ncol))
+        self._check(self._fn("eval_metabolics")(self.ctx, len(idx), abi.iptr(idx), abi.iptr(col), abi.dptr(w), npts,
+                                                abi.dptr(inputs), abi.dptr(out)))
+        return out[:npts]
 
     def eval_g(self, x, new_x=True):
         x = np.ascontiguousarray(x, float)
