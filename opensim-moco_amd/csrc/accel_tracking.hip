@@ -4,34 +4,10 @@
 // and accelerations.  The accelerations are the iterate's (implicit multibody
 // dynamics: the kernel has no interpreter in it) or the udot of one run of the
 // generic interpreter (explicit dynamics).  One instantiation per size class and
-// dynamics mode, selected by accel_tracking_backends()[size_class] whatever back
-// end serves g and J.  A translation unit of its own, as joint_reaction.hip:
+// dynamics mode, selected by the context's size class whatever back end serves
+// g and J.  A translation unit of its own, as joint_reaction.hip:
 // generic.hip compiles to the code it had without it.
-#include "core.hpp"
-
-// The point inputs of one grid point where they lie (x, or a probe row) with a
-// lane's perturbation applied on the fly, lane_inputs' arithmetic (in[i] + step)
-// with nothing staged per thread: states, controls and derivative variables
-// only (what the goal reads: q, u and the acceleration variables).
-struct AccelIn {
-    const double* __restrict__ xs;
-    const double* __restrict__ xc;
-    const double* __restrict__ xd;
-    int NS, NC, pi;
-    double step;
-    __device__ __forceinline__ double operator[](int i) const {
-#pragma clang fp contract(off)
-        const double v = i < NS ? xs[i] : (i < NS + NC ? xc[i - NS] : xd[i - NS - NC]);
-        return i == pi ? v + step : v;
-    }
-};
-// Inputs o, o + 1, ... of an AccelIn: the speeds (o = nq) and the acceleration
-// variables (o = NS + NC).
-struct AccelInAt {
-    const AccelIn& in;
-    int o;
-    __device__ __forceinline__ double operator[](int j) const { return in[o + j]; }
-};
+#include "goal_lanes.hpp"
 
 // One body of the forward kinematic pass of dae_eval (dae_device.hpp) with
 // accelerations, restated: the parent's pose (Rp, pp), spatial velocity V and
@@ -223,49 +199,21 @@ __global__ void __launch_bounds__(64) k_accel_tracking(DevModel M, Layout L, Lan
         [[clang::always_inline]] dae_eval<Z::MB, Z::MQ, Z::MP>(M, w, t, in, in + M.ns, out, nullptr);
         accel_tracking_goals(M, GS, nat, t, in, in + M.nq, out, qk, Ck, lv + gid * nat);
     } else {
-        AccelIn in{x + 2 + (long)k * L.NS, x + 2 + (long)L.NS * L.G + (long)k * L.NC, x + L.DB + (long)k * L.NDV,
-                   L.NS, L.NC, -1, 0.0};
+        PointIn in = point_in(L, x, k);
         const double t = lane_time(Ln, grid[k], x[0], x[1], r, in.pi, in.step);
-        accel_tracking_goals(M, GS, nat, t, in, AccelInAt{in, M.nq}, AccelInAt{in, L.NS + L.NC}, qk, Ck,
+        accel_tracking_goals(M, GS, nat, t, in, PointInAt{in, M.nq}, PointInAt{in, L.NS + L.NC}, qk, Ck,
                 lv + gid * nat);
     }
 }
-// One thread per (grid point, direction): the quotients of k_accel_tracking's
-// lane values with k_grad's formulas and arithmetic, G.weight * dur * quad[k]
-// * dL added to what k_grad, k_marker_tracking and k_joint_reaction_grad left
-// in grad / tpart (after them on the same stream: one writer per entry and
-// launch); direction 0 also writes the goals' integrand slots of C.  A
-// direction that is not live writes nothing: its entry keeps its bits.
-__global__ void __launch_bounds__(64) k_accel_tracking_grad(Layout L, Lanes Ln, GoalSet GS, int nat,
-        const int* __restrict__ live, const double* __restrict__ x, const double* __restrict__ quad,
-        const double* __restrict__ lv, double* __restrict__ C, double* __restrict__ grad,
-        double* __restrict__ tpart) {
-#pragma clang fp contract(off)
-    const int ND = Ln.ND;
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= (long)L.G * ND) return;
-    const int k = (int)(tid / ND), d = (int)(tid % ND);
-    if (!live[d]) return;
-    const double dur = x[1] - x[0], h = Ln.h;
-    const double* lk = lv + (long)k * Ln.stride * nat;
-    double acc = 0.0;
-    int j = 0;
-    for (int g = 0; g < GS.ngoals && j < nat; ++g) {
-        const mh_goal G = GS.goals[g];
-        if (G.kind != MH_GOAL_ACCELERATION_TRACKING) continue;
-        const double l0 = lk[(long)Ln.base * nat + j], l1 = lk[(long)d * nat + j];
-        const double dL = Ln.fd == MH_FD_CENTRAL ? (l1 - lk[(long)(ND + d) * nat + j]) / (2.0 * h)
-                        : (Ln.fd == MH_FD_FORWARD ? (l1 - l0) / h : (l0 - l1) / h);
-        acc += G.weight * dur * quad[k] * dL;
-        if (d == 0) C[(long)k * GS.ngoals + g] = quad[k] * l0;
-        ++j;
-    }
-    if (d < 2) tpart[(long)k * 2 + d] += acc;
-    else if (d - 2 < L.NS) grad[2 + (long)k * L.NS + (d - 2)] += acc;
-    else if (d - 2 < L.NS + L.NC) grad[2 + (long)L.NS * L.G + (long)k * L.NC + (d - 2 - L.NS)] += acc;
-    else if (d - 2 < L.NS + L.NC + L.NDV) grad[L.DB + (long)k * L.NDV + (d - 2 - L.NS - L.NC)] += acc;
-    else grad[L.XM + (long)k * L.NM + (d - 2 - L.NS - L.NC - L.NDV)] += acc;
-}
+// The family's part of k_lane_goal_grad (goal_lanes.hpp): liveness is per
+// direction, the table k_accel_tracking skips lanes by, whatever the goal.
+struct AccelTrackingGoals : OneEntryPerGoal {
+    static constexpr int kind = MH_GOAL_ACCELERATION_TRACKING;
+    struct Args {
+        const int* __restrict__ live;
+    };
+    __device__ static bool live(const Args& A, const GoalSet&, int, int d) { return A.live[d]; }
+};
 // mh_eval_frame_accelerations: one thread per input row [time, NI point
 // inputs], the acceleration of every frame of goal g, out[row][frame][3].
 template <class Z, bool EXPLICIT>
@@ -291,11 +239,11 @@ __global__ void __launch_bounds__(64) k_accel_tracking_probe(DevModel M, Layout 
             for (int i = 0; i < 3; ++i) o[3 * f + i] = a[i];
         }
     } else {
-        const AccelIn v{row + 1, row + 1 + L.NS, row + 1 + L.NS + L.NC, L.NS, L.NC, -1, 0.0};
+        const PointIn v{row + 1, row + 1 + L.NS, row + 1 + L.NS + L.NC, L.NS, L.NC, -1, 0.0};
         for (int f = 0; f < nf; ++f) {
             const int tb = G.term_begin + 4 * f, b = GS.gidx[tb];
             double a[3] = {0.0, 0.0, 0.0};
-            if (b >= 0) frame_acceleration(M, v, AccelInAt{v, M.nq}, AccelInAt{v, L.NS + L.NC}, b, GS.gw + tb, a);
+            if (b >= 0) frame_acceleration(M, v, PointInAt{v, M.nq}, PointInAt{v, L.NS + L.NC}, b, GS.gw + tb, a);
             for (int i = 0; i < 3; ++i) o[3 * f + i] = a[i];
         }
     }
@@ -303,22 +251,16 @@ __global__ void __launch_bounds__(64) k_accel_tracking_probe(DevModel M, Layout 
 
 template <class Z, bool EXPLICIT>
 static void launch_accel_tracking(mh_ctx* c, const double* x, int mode) {
-    Layout L = make_layout(c, 0, c->G);
-    if (mode == 0) {
-        // base lanes only: c->g_block lanes per workgroup, as eval_g's k_eval
-        const Lanes ln{c->fd, c->lanes_at.ND, 1, 0, c->h};
-        const int tb = c->g_block;
-        hipLaunchKernelGGL((k_accel_tracking<Z, EXPLICIT>), dim3((unsigned)((c->G + tb - 1) / tb)), dim3(tb), 0,
-                c->stream, c->M, L, ln, c->GS, c->nat, (const int*)nullptr, x, c->d_grid, c->d_quad, c->d_C,
-                c->d_at);
-        return;
-    }
-    const Lanes& ln = c->lanes_at;
-    const long lanes = (long)c->G * ln.stride, dirs = (long)c->G * ln.ND;
-    hipLaunchKernelGGL((k_accel_tracking<Z, EXPLICIT>), dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, c->stream,
-            c->M, L, ln, c->GS, c->nat, c->d_at_live, x, c->d_grid, c->d_quad, (double*)nullptr, c->d_at);
-    hipLaunchKernelGGL(k_accel_tracking_grad, dim3((unsigned)((dirs + 63) / 64)), dim3(64), 0, c->stream, L, ln,
-            c->GS, c->nat, c->d_at_live, x, c->d_quad, c->d_at, c->d_C, c->d_grad, c->d_tpart);
+    const LaneGoals& R = c->lane_goals[LG_ACCEL_TRACKING];
+    launch_lane_goal_family<AccelTrackingGoals>(c, LG_ACCEL_TRACKING, {c->d_at_live}, x, mode,
+            [&](const Layout& L, const Lanes& ln, int mode) {
+                // objective mode: c->g_block lanes per workgroup, as eval_g's k_eval, and every lane live
+                const int tb = mode ? 64 : c->g_block;
+                const long lanes = (long)c->G * ln.stride;
+                hipLaunchKernelGGL((k_accel_tracking<Z, EXPLICIT>), dim3((unsigned)((lanes + tb - 1) / tb)), dim3(tb),
+                        0, c->stream, c->M, L, ln, c->GS, R.entries, mode ? c->d_at_live : (const int*)nullptr, x,
+                        c->d_grid, c->d_quad, mode ? (double*)nullptr : c->d_C, R.lv);
+            });
 }
 template <class Z>
 static void be_accel_tracking(mh_ctx* c, const double* x, int mode) {
@@ -336,12 +278,16 @@ static void be_accel_tracking_probe(mh_ctx* c, int goal, int np, const double* i
                 c->GS, goal, np, in, out);
 }
 
-const AccelTrackingBackend* accel_tracking_backends() {
-    static const AccelTrackingBackend kAccelTracking[4] = {
-        {&be_accel_tracking<SzSmall>, &be_accel_tracking_probe<SzSmall>},
-        {&be_accel_tracking<SzMedium>, &be_accel_tracking_probe<SzMedium>},
-        {&be_accel_tracking<SzLarge>, &be_accel_tracking_probe<SzLarge>},
-        {&be_accel_tracking<SzBody>, &be_accel_tracking_probe<SzBody>},
-    };
-    return kAccelTracking;
+const LaneGoalFamily& accel_tracking_goals() {
+    static const LaneGoalFamily kFamily = {
+        AccelTrackingGoals::kind,
+        {&be_accel_tracking<SzSmall>, &be_accel_tracking<SzMedium>, &be_accel_tracking<SzLarge>,
+         &be_accel_tracking<SzBody>}};
+    return kFamily;
+}
+void accel_tracking_probe(mh_ctx* c, int goal, int np, const double* in, double* out) {
+    static constexpr decltype(&be_accel_tracking_probe<SzSmall>) kProbe[4] = {
+        &be_accel_tracking_probe<SzSmall>, &be_accel_tracking_probe<SzMedium>, &be_accel_tracking_probe<SzLarge>,
+        &be_accel_tracking_probe<SzBody>};
+    kProbe[c->size_class](c, goal, np, in, out);
 }

@@ -2207,10 +2207,10 @@ __host__ __device__ __forceinline__ bool goal_tracked_items(int kind) {
 // costs (final time, final marker) and the marker / frame tracking goals, whose
 // integrand and gradient k_marker_tracking writes into the same slots.  The
 // joint-reaction goal (kind 14) is an integral goal: goal_integrand gives 0.0
-// for it, and k_joint_reaction / k_joint_reaction_grad write its slot and add
-// its gradient after k_integrand / k_grad.  The acceleration-tracking goal
-// (kind 15) likewise, by k_accel_tracking / k_accel_tracking_grad, and the
-// muscle-output goal (kind 17) by k_muscle_outputs / k_muscle_outputs_grad.
+// for it, and k_joint_reaction / k_lane_goal_grad (goal_lanes.hpp) write its
+// slot and add its gradient after k_integrand / k_grad.  The
+// acceleration-tracking goal (kind 15) likewise, by k_accel_tracking, and the
+// muscle-output goal (kind 17) by k_muscle_outputs.
 __host__ __device__ __forceinline__ bool goal_integral(int kind) {
     return kind != MH_GOAL_FINAL_TIME && kind != MH_GOAL_MARKER_FINAL && !goal_tracked_items(kind);
 }
@@ -2428,6 +2428,19 @@ struct TaskSet {
 struct Backend;
 struct GenEntry;
 
+// The goal families evaluated on finite-difference lanes of their own, in
+// launch order: MocoJointReactionGoal (kind 14), MocoAccelerationTrackingGoal
+// (15), MocoOutputGoal over a muscle output (17) and over a
+// Bhargava2004Metabolics output (18).
+enum LaneGoalKind { LG_JOINT_REACTION, LG_ACCEL_TRACKING, LG_MUSCLE_OUTPUTS, LG_METABOLICS, LG_COUNT };
+// A family in a context: its goals, the lane values all of them occupy (one
+// per goal; a metabolics goal one per muscle, concatenated in goal order) and
+// its lane kernel's values [G][stride][entries].
+struct LaneGoals {
+    int ngoals = 0, entries = 0;
+    double* lv = nullptr;
+};
+
 struct mh_ctx {
     // problem
     int NQ = 0, NZ = 0, NS = 0, NC = 0, NO = 0, NI = 0;
@@ -2587,32 +2600,14 @@ struct mh_ctx {
     MarkerTrack MT{};
     std::vector<int> mt_tab;
     size_t mt_lds[2] = {0, 0};
-    // joint-reaction goals (kind 14): their count, the lanes of
-    // k_joint_reaction in gradient mode (ND = NI - NSL + 2) and its lane
-    // values [G][stride][njr]
-    int njr = 0;
-    Lanes lanes_jr{};
-    double* d_jr = nullptr;
-    // acceleration-tracking goals (kind 15): their count, the lanes of
-    // k_accel_tracking in gradient mode (ND = NI - NSL + 2), its lane values
-    // [G][stride][nat] and the directions that can change a goal's integrand
-    // [ND] (implicit dynamics: t0, tf and the tracked chains' coordinates,
-    // speeds and acceleration variables; explicit: all)
-    int nat = 0;
-    Lanes lanes_at{};
-    double* d_at = nullptr;
+    // the goals evaluated on lanes of their own (LaneGoalFamily): the lanes
+    // of their kernels in gradient mode (ND = NI - NSL + 2), each family's
+    // record, and the directions that can change an acceleration-tracking
+    // goal's integrand [ND] (implicit dynamics: t0, tf and the tracked
+    // chains' coordinates, speeds and acceleration variables; explicit: all)
+    Lanes goal_lanes{};
+    LaneGoals lane_goals[LG_COUNT];
     const int* d_at_live = nullptr;
-    // muscle-output goals (kind 17): their count, the lanes of
-    // k_muscle_outputs in gradient mode (ND = NI - NSL + 2) and its lane
-    // values [G][stride][nmo]
-    int nmo = 0;
-    Lanes lanes_mo{};
-    double* d_mo = nullptr;
-    // metabolics goals (kind 18): their count, the muscle entries of all of
-    // them concatenated in goal order, and k_metabolics' lane values
-    // [G][stride][nmet_entries] (the lanes are lanes_mo)
-    int nmet = 0, nmet_entries = 0;
-    double* d_met = nullptr;
     bool use_roles = false;        // MOCOHIP_ROLES=1: k_role (+ k_couple) for the Jacobian lanes
     int role_threads = 256;        // k_role workgroup size (MOCOHIP_ROLE_THREADS: 64..512)
     int iv_threads = 1024;         // k_interval workgroup size, Jacobian lanes (MOCOHIP_IV_THREADS: 256..1024)
@@ -3077,45 +3072,34 @@ static constexpr Backend make_backend_tasks(const char* name, double flops) {
 
 // Generic device-interpreter back ends (generic.hip), one per size class.
 const Backend* generic_backends();
-// The joint-reaction goals' kernels (joint_reaction.hip), by size class as
-// generic_backends(): they run the generic interpreter whatever back end
-// serves g and J (a generated back end has no body-level forces to read).
-// eval: the goals' integrands (mode 0) or integrands and gradient parts (mode
-// 1); probe: mh_eval_joint_reaction's rows.  A translation unit of their own,
-// so that generic.hip compiles to the code it had without them (the inlining
-// of dae_eval into k_eval_lds depends on the unit's other call sites).
-struct JointReactionBackend {
-    void (*eval)(mh_ctx*, const double* x, int mode);
-    void (*probe)(mh_ctx*, int goal, int np, const double* in, double* out);
+// The kernels of a lane-goal family (enum LaneGoalKind), by size class as
+// generic_backends(): the goals' integrands (mode 0) or integrands and
+// gradient parts (mode 1).  The joint-reaction goals' run the generic
+// interpreter whatever back end serves g and J (a generated back end has no
+// body-level forces to read); the acceleration-tracking goals' entries pick
+// the instantiation of the context's dynamics mode.  Each family is a
+// translation unit of its own, so that generic.hip compiles to the code it had
+// without them (the inlining of dae_eval into k_eval_lds depends on the unit's
+// other call sites).
+struct LaneGoalFamily {
+    int kind;   // MH_GOAL_*
+    void (*eval[4])(mh_ctx*, const double* x, int mode);
 };
-const JointReactionBackend* joint_reaction_backends();
-// The acceleration-tracking goals' kernels (accel_tracking.hip), selected and
-// kept apart in the same way.  eval: the goals' integrands (mode 0) or
-// integrands and gradient parts (mode 1); probe: mh_eval_frame_accelerations'
-// rows.  Each entry picks the instantiation of the context's dynamics mode.
-struct AccelTrackingBackend {
-    void (*eval)(mh_ctx*, const double* x, int mode);
-    void (*probe)(mh_ctx*, int goal, int np, const double* in, double* out);
-};
-const AccelTrackingBackend* accel_tracking_backends();
-// The muscle-output goals' kernels (muscle_outputs.hip), selected and kept
-// apart in the same way.  eval: the goals' integrands (mode 0) or integrands
-// and gradient parts (mode 1); probe: mh_eval_muscle_outputs' rows (mus /
-// which: device arrays of nout muscles and outputs).
-struct MuscleOutputsBackend {
-    void (*eval)(mh_ctx*, const double* x, int mode);
-    void (*probe)(mh_ctx*, int nout, const int* mus, const int* which, int np, const double* in, double* out);
-};
-const MuscleOutputsBackend* muscle_outputs_backends();
-// The metabolics goals' kernels (metabolics.hip), likewise.  eval: mode 0 / 1
-// as above; probe: mh_eval_metabolics' rows (one component's term block of nm
+const LaneGoalFamily& joint_reaction_goals();
+const LaneGoalFamily& accel_tracking_goals();
+const LaneGoalFamily& muscle_output_goals();
+const LaneGoalFamily& metabolics_goals();
+// The families' probes, by the context's size class: the rows of
+// mh_eval_joint_reaction, of mh_eval_frame_accelerations, of
+// mh_eval_muscle_outputs (mus / which: device arrays of nout muscles and
+// outputs) and of mh_eval_metabolics (one component's term block of nm
 // muscles in device arrays, 5 + nm values per row).
-struct MetabolicsBackend {
-    void (*eval)(mh_ctx*, const double* x, int mode);
-    void (*probe)(mh_ctx*, int nm, const int* idx, const int* col, const double* w, int np, const double* in,
-                  double* out);
-};
-const MetabolicsBackend* metabolics_backends();
+void joint_reaction_probe(mh_ctx*, int goal, int np, const double* in, double* out);
+void accel_tracking_probe(mh_ctx*, int goal, int np, const double* in, double* out);
+void muscle_outputs_probe(mh_ctx*, int nout, const int* mus, const int* which, int np, const double* in,
+        double* out);
+void metabolics_probe(mh_ctx*, int nm, const int* idx, const int* col, const double* w, int np, const double* in,
+        double* out);
 // A metabolics term block (include/mocohip.h MH_GOAL_METABOLICS): six header
 // terms, then six per muscle.
 #define MH_MET_HEADER 6

@@ -2,8 +2,8 @@
 // MH_GOAL_JOINT_REACTION): the generic interpreter (dae_device.hpp) run with
 // the point's accelerations per finite-difference lane, and the joint load
 // read from its workspace.  One instantiation per size class, selected by
-// joint_reaction_backends()[size_class] whatever back end serves g and J.
-#include "core.hpp"
+// the context's size class whatever back end serves g and J.
+#include "goal_lanes.hpp"
 
 // ---- MocoJointReactionGoal (include/mocohip.h MH_GOAL_JOINT_REACTION) -------
 // The reaction load r (moment x, y, z, force x, y, z) of goal G from the
@@ -96,39 +96,13 @@ __global__ void __launch_bounds__(64) k_joint_reaction(DevModel M, Layout L, Lan
         ++j;
     }
 }
-// One thread per (grid point, direction): the quotients of k_joint_reaction's
-// lane values with k_grad's formulas and arithmetic, G.weight * dur * quad[k]
-// * dL added to what k_grad and k_marker_tracking left in grad / tpart (after
-// them on the same stream: one writer per entry and launch); direction 0 also
-// writes the goals' integrand slots of C.
-__global__ void __launch_bounds__(64) k_joint_reaction_grad(Layout L, Lanes Ln, GoalSet GS, int njr,
-        const double* __restrict__ x, const double* __restrict__ quad, const double* __restrict__ lv,
-        double* __restrict__ C, double* __restrict__ grad, double* __restrict__ tpart) {
-#pragma clang fp contract(off)
-    const int ND = Ln.ND;
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= (long)L.G * ND) return;
-    const int k = (int)(tid / ND), d = (int)(tid % ND);
-    const double dur = x[1] - x[0], h = Ln.h;
-    const double* lk = lv + (long)k * Ln.stride * njr;
-    double acc = 0.0;
-    int j = 0;
-    for (int g = 0; g < GS.ngoals && j < njr; ++g) {
-        const mh_goal G = GS.goals[g];
-        if (G.kind != MH_GOAL_JOINT_REACTION) continue;
-        const double l0 = lk[(long)Ln.base * njr + j], l1 = lk[(long)d * njr + j];
-        const double dL = Ln.fd == MH_FD_CENTRAL ? (l1 - lk[(long)(ND + d) * njr + j]) / (2.0 * h)
-                        : (Ln.fd == MH_FD_FORWARD ? (l1 - l0) / h : (l0 - l1) / h);
-        acc += G.weight * dur * quad[k] * dL;
-        if (d == 0) C[(long)k * GS.ngoals + g] = quad[k] * l0;
-        ++j;
-    }
-    if (d < 2) tpart[(long)k * 2 + d] += acc;
-    else if (d - 2 < L.NS) grad[2 + (long)k * L.NS + (d - 2)] += acc;
-    else if (d - 2 < L.NS + L.NC) grad[2 + (long)L.NS * L.G + (long)k * L.NC + (d - 2 - L.NS)] += acc;
-    else if (d - 2 < L.NS + L.NC + L.NDV) grad[L.DB + (long)k * L.NDV + (d - 2 - L.NS - L.NC)] += acc;
-    else grad[L.XM + (long)k * L.NM + (d - 2 - L.NS - L.NC - L.NDV)] += acc;
-}
+// The family's part of k_lane_goal_grad (goal_lanes.hpp): every direction is
+// live for every goal, so every entry gets its sum added, a zero included.
+struct JointReactionGoals : OneEntryPerGoal {
+    static constexpr int kind = MH_GOAL_JOINT_REACTION;
+    struct Args {};
+    __device__ static bool live(const Args&, const GoalSet&, int, int) { return true; }
+};
 // mh_eval_joint_reaction: one thread per input row [time, NI point inputs],
 // the six components of goal g's load.
 template <class Z>
@@ -150,21 +124,16 @@ __global__ void __launch_bounds__(64) k_joint_reaction_probe(DevModel M, Layout 
 
 template <class Z>
 static void be_joint_reaction(mh_ctx* c, const double* x, int mode) {
-    Layout L = make_layout(c, 0, c->G);
-    if (mode == 0) {
-        // base lanes only: c->g_block lanes per workgroup, as eval_g's k_eval
-        const Lanes ln{c->fd, c->lanes_jr.ND, 1, 0, c->h};
-        const int tb = c->g_block;
-        hipLaunchKernelGGL(k_joint_reaction<Z>, dim3((unsigned)((c->G + tb - 1) / tb)), dim3(tb), 0, c->stream,
-                c->M, L, ln, c->GS, c->njr, x, c->d_grid, c->d_quad, c->d_C, c->d_jr);
-        return;
-    }
-    const Lanes& ln = c->lanes_jr;
-    const long lanes = (long)c->G * ln.stride, dirs = (long)c->G * ln.ND;
-    hipLaunchKernelGGL(k_joint_reaction<Z>, dim3((unsigned)((lanes + 63) / 64)), dim3(64), 0, c->stream, c->M, L,
-            ln, c->GS, c->njr, x, c->d_grid, c->d_quad, (double*)nullptr, c->d_jr);
-    hipLaunchKernelGGL(k_joint_reaction_grad, dim3((unsigned)((dirs + 63) / 64)), dim3(64), 0, c->stream, L, ln,
-            c->GS, c->njr, x, c->d_quad, c->d_jr, c->d_C, c->d_grad, c->d_tpart);
+    const LaneGoals& R = c->lane_goals[LG_JOINT_REACTION];
+    launch_lane_goal_family<JointReactionGoals>(c, LG_JOINT_REACTION, {}, x, mode,
+            [&](const Layout& L, const Lanes& ln, int mode) {
+                // objective mode: c->g_block lanes per workgroup, as eval_g's k_eval
+                const int tb = mode ? 64 : c->g_block;
+                const long lanes = (long)c->G * ln.stride;
+                hipLaunchKernelGGL(k_joint_reaction<Z>, dim3((unsigned)((lanes + tb - 1) / tb)), dim3(tb), 0,
+                        c->stream, c->M, L, ln, c->GS, R.entries, x, c->d_grid, c->d_quad,
+                        mode ? (double*)nullptr : c->d_C, R.lv);
+            });
 }
 template <class Z>
 static void be_joint_reaction_probe(mh_ctx* c, int goal, int np, const double* in, double* out) {
@@ -173,12 +142,16 @@ static void be_joint_reaction_probe(mh_ctx* c, int goal, int np, const double* i
             goal, np, in, out);
 }
 
-const JointReactionBackend* joint_reaction_backends() {
-    static const JointReactionBackend kJointReaction[4] = {
-        {&be_joint_reaction<SzSmall>, &be_joint_reaction_probe<SzSmall>},
-        {&be_joint_reaction<SzMedium>, &be_joint_reaction_probe<SzMedium>},
-        {&be_joint_reaction<SzLarge>, &be_joint_reaction_probe<SzLarge>},
-        {&be_joint_reaction<SzBody>, &be_joint_reaction_probe<SzBody>},
-    };
-    return kJointReaction;
+const LaneGoalFamily& joint_reaction_goals() {
+    static const LaneGoalFamily kFamily = {
+        JointReactionGoals::kind,
+        {&be_joint_reaction<SzSmall>, &be_joint_reaction<SzMedium>, &be_joint_reaction<SzLarge>,
+         &be_joint_reaction<SzBody>}};
+    return kFamily;
+}
+void joint_reaction_probe(mh_ctx* c, int goal, int np, const double* in, double* out) {
+    static constexpr decltype(&be_joint_reaction_probe<SzSmall>) kProbe[4] = {
+        &be_joint_reaction_probe<SzSmall>, &be_joint_reaction_probe<SzMedium>, &be_joint_reaction_probe<SzLarge>,
+        &be_joint_reaction_probe<SzBody>};
+    kProbe[c->size_class](c, goal, np, in, out);
 }

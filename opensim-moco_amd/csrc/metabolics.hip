@@ -6,11 +6,10 @@
 // touches, the path's length and lengthening speed, ONE evaluation of the
 // muscle (dgf_outputs: all the quantities the model reads), then the muscle's
 // activation, maintenance and shortening heat rates and its mechanical work
-// rate.  The sum over a goal's muscles is taken by k_metabolics_grad /
-// k_metabolics_sum in the component's muscle order, one thread per value, so
+// rate.  The sum over a goal's muscles is taken by k_lane_goal_grad
+// (goal_lanes.hpp) / k_metabolics_sum in the component's muscle order, one thread per value, so
 // the result has the same bits on every run.  One instantiation per size
-// class, selected by metabolics_backends()[size_class] whatever back end
-// serves g and J.  A translation unit of its own, as muscle_outputs.hip.
+// class, selected by the context's whatever back end serves g and J.  A translation unit of its own, as muscle_outputs.hip.
 #include "mo_device.hpp"
 
 // Option flags of a component (goal_index of the block's first term).
@@ -174,8 +173,7 @@ __global__ void __launch_bounds__(64) k_metabolics(DevModel M, Layout L, Lanes L
     if (H.output == MH_MET_MUSCLE_METABOLIC_RATE && m != H.channel) return;
     const int im = GS.gidx[mb];
     if (!base && !met_live(M, im, dir)) return;
-    MoIn in{x + 2 + (long)k * L.NS, x + 2 + (long)L.NS * L.G + (long)k * L.NC, x + L.DB + (long)k * L.NDV, L.NS, L.NC,
-            -1, 0.0};
+    PointIn in = point_in(L, x, k);
     const double t = lane_time(Ln, grid[k], x[0], x[1], r, in.pi, in.step);
     Pose X[Z::MB + 1];
     SV V[Z::MB + 1];
@@ -240,50 +238,23 @@ __global__ void __launch_bounds__(64) k_metabolics_sum(DevModel M, Layout L, Goa
     }
 }
 
-// One thread per (grid point, direction): the quotients of the goals' lane
-// sums with k_grad's formulas and arithmetic, G.weight * dur * quad[k] * dL of
-// the goals the direction is live for, added to what the other goal kernels
-// left in grad / tpart (after them on the same stream: one writer per entry
-// and launch); direction 0 also writes the goals' integrand slots of C.  A
-// direction live for no muscle of any goal writes nothing.
-__global__ void __launch_bounds__(64) k_metabolics_grad(DevModel M, Layout L, Lanes Ln, GoalSet GS, int nent,
-        const double* __restrict__ x, const double* __restrict__ quad, const double* __restrict__ lv,
-        double* __restrict__ C, double* __restrict__ grad, double* __restrict__ tpart) {
-#pragma clang fp contract(off)
-    const int ND = Ln.ND;
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= (long)L.G * ND) return;
-    const int k = (int)(tid / ND), d = (int)(tid % ND);
-    const double dur = x[1] - x[0], h = Ln.h;
-    const double* lk = lv + (long)k * Ln.stride * nent;
-    double acc = 0.0;
-    bool any = false;
-    int e0 = 0;
-    for (int g = 0; g < GS.ngoals; ++g) {
-        const mh_goal G = GS.goals[g];
-        if (G.kind != MH_GOAL_METABOLICS) continue;
-        if (met_goal_live(M, GS, g, d)) {
-            const double l1 = met_goal_value(M, GS, Ln, g, e0, nent, lk, d);
-            double dL;
-            if (Ln.fd == MH_FD_CENTRAL) {
-                dL = (l1 - met_goal_value(M, GS, Ln, g, e0, nent, lk, ND + d)) / (2.0 * h);
-            } else {
-                const double l0 = met_goal_value(M, GS, Ln, g, e0, nent, lk, Ln.base);
-                dL = Ln.fd == MH_FD_FORWARD ? (l1 - l0) / h : (l0 - l1) / h;
-            }
-            acc += G.weight * dur * quad[k] * dL;
-            any = true;
-            if (d == 0) C[(long)k * GS.ngoals + g] = quad[k] * met_goal_value(M, GS, Ln, g, e0, nent, lk, Ln.base);
-        }
-        e0 += (G.term_count - MH_MET_HEADER) / MH_MET_PER_MUSCLE;
+// The family's part of k_lane_goal_grad (goal_lanes.hpp): a goal occupies one
+// lane value per muscle and its value at a lane is their sum (met_goal_value);
+// a direction is live for it where it is for one of its muscles.
+struct MetabolicsGoals {
+    static constexpr int kind = MH_GOAL_METABOLICS;
+    struct Args {
+        DevModel M;
+    };
+    __device__ static int entries(const mh_goal& G) { return (G.term_count - MH_MET_HEADER) / MH_MET_PER_MUSCLE; }
+    __device__ static bool live(const Args& A, const GoalSet& GS, int g, int d) {
+        return met_goal_live(A.M, GS, g, d);
     }
-    if (!any) return;
-    if (d < 2) tpart[(long)k * 2 + d] += acc;
-    else if (d - 2 < L.NS) grad[2 + (long)k * L.NS + (d - 2)] += acc;
-    else if (d - 2 < L.NS + L.NC) grad[2 + (long)L.NS * L.G + (long)k * L.NC + (d - 2 - L.NS)] += acc;
-    else if (d - 2 < L.NS + L.NC + L.NDV) grad[L.DB + (long)k * L.NDV + (d - 2 - L.NS - L.NC)] += acc;
-    else grad[L.XM + (long)k * L.NM + (d - 2 - L.NS - L.NC - L.NDV)] += acc;
-}
+    __device__ static double value(const Args& A, const GoalSet& GS, const Lanes& Ln, int g,
+            const double* __restrict__ lk, int nent, int e, int r) {
+        return met_goal_value(A.M, GS, Ln, g, e, nent, lk, r);
+    }
+};
 
 // mh_eval_metabolics: one thread per input row [time, NI point inputs]; the
 // component's block (nm muscles) -> [total metabolic rate (with the basal
@@ -297,7 +268,7 @@ __global__ void __launch_bounds__(64) k_metabolics_probe(DevModel M, Layout L, i
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npts) return;
     const double* row = inp + (long)p * (1 + L.NI);
-    const MoIn in{row + 1, row + 1 + L.NS, row + 1 + L.NS + L.NC, L.NS, L.NC, -1, 0.0};
+    const PointIn in{row + 1, row + 1 + L.NS, row + 1 + L.NS + L.NC, L.NS, L.NC, -1, 0.0};
     const MetHeader H = met_header(idx, col, w);
     unsigned long long mask = 0ull;
     for (int m = 0; m < nm; ++m) mask |= mo_muscle_bodies(M, idx[MH_MET_HEADER + MH_MET_PER_MUSCLE * m]);
@@ -324,23 +295,16 @@ __global__ void __launch_bounds__(64) k_metabolics_probe(DevModel M, Layout L, i
 
 template <class Z>
 static void be_metabolics(mh_ctx* c, const double* x, int mode) {
-    Layout L = make_layout(c, 0, c->G);
-    const int nent = c->nmet_entries;
-    if (mode == 0) {
-        // base lanes only, then the sums
-        const Lanes ln{c->fd, c->lanes_mo.ND, 1, 0, c->h};
-        hipLaunchKernelGGL(k_metabolics<Z>, dim3((unsigned)(((long)c->G * nent + 63) / 64)), dim3(64), 0, c->stream,
-                c->M, L, ln, c->GS, nent, x, c->d_grid, c->d_met);
-        hipLaunchKernelGGL(k_metabolics_sum, dim3((unsigned)((c->G + 63) / 64)), dim3(64), 0, c->stream, c->M, L, c->GS,
-                nent, c->d_quad, c->d_met, c->d_C);
-        return;
-    }
-    const Lanes& ln = c->lanes_mo;
-    const long lanes = (long)c->G * ln.stride, dirs = (long)c->G * ln.ND;
-    hipLaunchKernelGGL(k_metabolics<Z>, dim3((unsigned)((lanes * nent + 63) / 64)), dim3(64), 0, c->stream, c->M, L, ln,
-            c->GS, nent, x, c->d_grid, c->d_met);
-    hipLaunchKernelGGL(k_metabolics_grad, dim3((unsigned)((dirs + 63) / 64)), dim3(64), 0, c->stream, c->M, L, ln,
-            c->GS, nent, x, c->d_quad, c->d_met, c->d_C, c->d_grad, c->d_tpart);
+    const LaneGoals& R = c->lane_goals[LG_METABOLICS];
+    launch_lane_goal_family<MetabolicsGoals>(c, LG_METABOLICS, {c->M}, x, mode,
+            [&](const Layout& L, const Lanes& ln, int mode) {
+                const long threads = (long)c->G * ln.stride * R.entries;
+                hipLaunchKernelGGL(k_metabolics<Z>, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, c->stream,
+                        c->M, L, ln, c->GS, R.entries, x, c->d_grid, R.lv);
+                if (mode == 0)   // objective mode: the goals' sums over their muscles
+                    hipLaunchKernelGGL(k_metabolics_sum, dim3((unsigned)((c->G + 63) / 64)), dim3(64), 0, c->stream,
+                            c->M, L, c->GS, R.entries, c->d_quad, R.lv, c->d_C);
+            });
 }
 template <class Z>
 static void be_metabolics_probe(mh_ctx* c, int nm, const int* idx, const int* col, const double* w, int np,
@@ -350,12 +314,16 @@ static void be_metabolics_probe(mh_ctx* c, int nm, const int* idx, const int* co
             np, in, out);
 }
 
-const MetabolicsBackend* metabolics_backends() {
-    static const MetabolicsBackend kMetabolics[4] = {
-        {&be_metabolics<SzSmall>, &be_metabolics_probe<SzSmall>},
-        {&be_metabolics<SzMedium>, &be_metabolics_probe<SzMedium>},
-        {&be_metabolics<SzLarge>, &be_metabolics_probe<SzLarge>},
-        {&be_metabolics<SzBody>, &be_metabolics_probe<SzBody>},
-    };
-    return kMetabolics;
+const LaneGoalFamily& metabolics_goals() {
+    static const LaneGoalFamily kFamily = {
+        MetabolicsGoals::kind,
+        {&be_metabolics<SzSmall>, &be_metabolics<SzMedium>, &be_metabolics<SzLarge>, &be_metabolics<SzBody>}};
+    return kFamily;
+}
+void metabolics_probe(mh_ctx* c, int nm, const int* idx, const int* col, const double* w, int np, const double* in,
+        double* out) {
+    static constexpr decltype(&be_metabolics_probe<SzSmall>) kProbe[4] = {
+        &be_metabolics_probe<SzSmall>, &be_metabolics_probe<SzMedium>, &be_metabolics_probe<SzLarge>,
+        &be_metabolics_probe<SzBody>};
+    kProbe[c->size_class](c, nm, idx, col, w, np, in, out);
 }

@@ -1,31 +1,10 @@
 // mo_device.hpp -- the velocity-stage device functions the muscle-output
 // kernels (muscle_outputs.hip) and the metabolics kernels (metabolics.hip)
-// share: a lane's inputs where they lie, the forward kinematic pass over the
-// bodies of a muscle's path, the path's length and lengthening speed, the
+// share (a lane's inputs where they lie are goal_lanes.hpp's PointIn): the
+// forward kinematic pass over the bodies of a muscle's path, the path's length and lengthening speed, the
 // muscle's own inputs and the directions that can change them.
 #pragma once
-#include "core.hpp"
-
-// The point inputs of one grid point where they lie (x, or a probe row) with a
-// lane's perturbation applied on the fly (lane_inputs' arithmetic: in[i] +
-// step): states, controls and derivative variables, all the outputs read.
-struct MoIn {
-    const double* __restrict__ xs;
-    const double* __restrict__ xc;
-    const double* __restrict__ xd;
-    int NS, NC, pi;
-    double step;
-    __device__ __forceinline__ double operator[](int i) const {
-#pragma clang fp contract(off)
-        const double v = i < NS ? xs[i] : (i < NS + NC ? xc[i - NS] : xd[i - NS - NC]);
-        return i == pi ? v + step : v;
-    }
-};
-struct MoInAt {
-    const MoIn& in;
-    int o;
-    __device__ __forceinline__ double operator[](int j) const { return in[o + j]; }
-};
+#include "goal_lanes.hpp"
 
 // One body of the forward kinematic pass of dae_eval (dae_device.hpp),
 // position and velocity parts: the parent's pose Pp and spatial velocity Vp (in
@@ -196,7 +175,7 @@ __device__ __forceinline__ void mo_path(const DevModel& M, int im, const Q& q, c
 // mus_ftn_state index [q, u, z]; with prescribed kinematics the NLP states are
 // z alone).
 __device__ __forceinline__ double mo_value(const DevModel& M, int im, int which, double L, double S,
-        const MoIn& in) {
+        const PointIn& in) {
     const int zo = M.presc ? 2 * M.nq : 0;
     const double exc = in[M.ns + M.mus_control[im]];
     const int sa = M.mus_act_state[im], sf = M.mus_ftn_state[im], id = M.mus_ider[im];
@@ -208,7 +187,7 @@ __device__ __forceinline__ double mo_value(const DevModel& M, int im, int which,
 
 // Every quantity of muscle im at once (dgf_outputs), its inputs picked as
 // mo_value picks them: the bits of mo_value's outputs.
-__device__ __forceinline__ DgfOut mo_all(const DevModel& M, int im, double L, double S, const MoIn& in) {
+__device__ __forceinline__ DgfOut mo_all(const DevModel& M, int im, double L, double S, const PointIn& in) {
     const int zo = M.presc ? 2 * M.nq : 0;
     const double exc = in[M.ns + M.mus_control[im]];
     const int sa = M.mus_act_state[im], sf = M.mus_ftn_state[im], id = M.mus_ider[im];
@@ -241,7 +220,7 @@ __device__ __forceinline__ bool mo_live(const DevModel& M, int im, int which, in
 // row, perturbed on the fly), or with prescribed kinematics the kinematics
 // table's at the lane's time, as GenericDae::eval_w takes them.
 template <class Z, class F>
-__device__ __forceinline__ void mo_with_kinematics(const DevModel& M, double t, const MoIn& in,
+__device__ __forceinline__ void mo_with_kinematics(const DevModel& M, double t, const PointIn& in,
         unsigned long long mask, Pose* X, SV* V, const F& body) {
     if (M.presc) {
         double q[Z::MQ], u[Z::MQ];
@@ -255,7 +234,7 @@ __device__ __forceinline__ void mo_with_kinematics(const DevModel& M, double t, 
         mo_kinematics<Z::MB>(M, q, u, mask, X, V);
         body(q, u);
     } else {
-        const MoInAt u{in, M.nq};
+        const PointInAt u{in, M.nq};
         mo_kinematics<Z::MB>(M, in, u, mask, X, V);
         body(in, u);
     }

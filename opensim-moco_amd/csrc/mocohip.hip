@@ -49,6 +49,13 @@ static int set_err(int code, const char* fmt, ...) {
             return set_err(MH_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(e_)); \
     } while (0)
 
+// The lane-goal families in launch order (enum LaneGoalKind).
+static const LaneGoalFamily& lane_goal_family(int f) {
+    static const LaneGoalFamily* const kFamilies[LG_COUNT] = {&joint_reaction_goals(), &accel_tracking_goals(),
+                                                              &muscle_output_goals(), &metabolics_goals()};
+    return *kFamilies[f];
+}
+
 extern "C" int mh_abi_version(void) { return MH_ABI_VERSION; }
 #ifndef MH_BUILD_ID
 #define MH_BUILD_ID "unknown"
@@ -2622,42 +2629,29 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     const size_t o_C = A.reserve(sizeof(double) * (size_t)c->G * std::max(1, c->ngoals));
     const size_t o_grad = A.reserve(sizeof(double) * c->n);
     const size_t o_tpart = A.reserve(sizeof(double) * 2 * (size_t)c->G);
-    // joint-reaction goals: k_joint_reaction's lanes and lane values
-    c->njr = 0;
-    for (const mh_goal& G : c->goals) c->njr += G.kind == MH_GOAL_JOINT_REACTION;
+    // the lane-goal families: their kernels' lanes, then per family its goals,
+    // the lane values they occupy and room for them, in launch order; the
+    // acceleration-tracking goals' live directions follow their lane values
     {
         const int NDj = c->NI - c->NSL + 2;
         const int sj = c->fd == MH_FD_CENTRAL ? 2 * NDj + 1 : NDj + 1;
-        c->lanes_jr = Lanes{c->fd, NDj, sj, sj - 1, c->h};
+        c->goal_lanes = Lanes{c->fd, NDj, sj, sj - 1, c->h};
     }
-    const size_t o_jr = c->njr ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_jr.stride * c->njr) : 0;
-    // acceleration-tracking goals: k_accel_tracking's lanes, lane values and
-    // live directions (the same lanes as the joint-reaction goals')
-    c->nat = 0;
-    for (const mh_goal& G : c->goals) c->nat += G.kind == MH_GOAL_ACCELERATION_TRACKING;
-    c->lanes_at = c->lanes_jr;
-    const size_t o_at = c->nat ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_at.stride * c->nat) : 0;
-    size_t o_atlive = 0;
-    if (c->nat) {
-        const std::vector<int> live = accel_tracking_live(c.get(), p);
-        o_atlive = A.put(live.data(), live.size());
-    }
-    // muscle-output goals: k_muscle_outputs' lanes and lane values (the same
-    // lanes as the joint-reaction goals')
-    c->nmo = 0;
-    for (const mh_goal& G : c->goals) c->nmo += G.kind == MH_GOAL_OUTPUT;
-    c->lanes_mo = c->lanes_jr;
-    const size_t o_mo = c->nmo ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_mo.stride * c->nmo) : 0;
-    // metabolics goals: k_metabolics' lane values, one per muscle entry, on
-    // the same lanes
-    c->nmet = c->nmet_entries = 0;
-    for (const mh_goal& G : c->goals)
-        if (G.kind == MH_GOAL_METABOLICS) {
-            ++c->nmet;
-            c->nmet_entries += (G.term_count - MH_MET_HEADER) / MH_MET_PER_MUSCLE;
+    size_t o_lg[LG_COUNT] = {0, 0, 0, 0}, o_atlive = 0;
+    for (int f = 0; f < LG_COUNT; ++f) {
+        LaneGoals& R = c->lane_goals[f];
+        R = LaneGoals{};
+        for (const mh_goal& G : c->goals)
+            if (G.kind == lane_goal_family(f).kind) {
+                ++R.ngoals;
+                R.entries += f == LG_METABOLICS ? (G.term_count - MH_MET_HEADER) / MH_MET_PER_MUSCLE : 1;
+            }
+        if (R.ngoals) o_lg[f] = A.reserve(sizeof(double) * (size_t)c->G * c->goal_lanes.stride * R.entries);
+        if (f == LG_ACCEL_TRACKING && R.ngoals) {
+            const std::vector<int> live = accel_tracking_live(c.get(), p);
+            o_atlive = A.put(live.data(), live.size());
         }
-    const size_t o_met =
-            c->nmet ? A.reserve(sizeof(double) * (size_t)c->G * c->lanes_mo.stride * c->nmet_entries) : 0;
+    }
     const size_t o_f = A.reserve(sizeof(double) * 4);
     const size_t o_epc = A.reserve(sizeof(double) * (size_t)std::max(1, c->ngoals));   // endpoint costs
     const int npts_iv = c->scheme == MH_HERMITE_SIMPSON ? 3 : 2;
@@ -2857,13 +2851,9 @@ extern "C" int mh_create(const mh_problem* p, const mh_options* o, mh_ctx** out)
     c->d_C = (double*)(b + o_C); c->d_grad = (double*)(b + o_grad); c->d_tpart = (double*)(b + o_tpart);
     c->d_f = (double*)(b + o_f);
     c->d_ep = (double*)(b + o_epc);
-    if (c->njr) c->d_jr = (double*)(b + o_jr);
-    if (c->nat) {
-        c->d_at = (double*)(b + o_at);
-        c->d_at_live = (const int*)(b + o_atlive);
-    }
-    if (c->nmo) c->d_mo = (double*)(b + o_mo);
-    if (c->nmet) c->d_met = (double*)(b + o_met);
+    for (int f = 0; f < LG_COUNT; ++f)
+        if (c->lane_goals[f].ngoals) c->lane_goals[f].lv = (double*)(b + o_lg[f]);
+    if (c->lane_goals[LG_ACCEL_TRACKING].ngoals) c->d_at_live = (const int*)(b + o_atlive);
     c->has_marker = false;
     for (int g = 0; g < p->ngoals; ++g) c->has_marker |= p->goals[g].kind == MH_GOAL_MARKER_FINAL;
     if (MT.nm > 0) MT.tab = (const int*)(b + o_mttab);
@@ -3886,30 +3876,13 @@ static void launch_marker_tracking(mh_ctx* c, const Layout& L, int mode) {
             c->d_quad, c->d_C, c->d_grad, c->d_tpart);
 }
 
-// The joint-reaction goals' integrands (mode 0) and their gradient parts too
-// (mode 1), after the other goals' kernels, by the generic interpreter's
-// kernels of the context's size class whatever back end serves g and J.
-static void launch_joint_reaction(mh_ctx* c, int mode) {
-    if (c->njr == 0) return;
-    joint_reaction_backends()[c->size_class].eval(c, c->d_x, mode);
-}
-
-// The acceleration-tracking goals' likewise, after the joint-reaction goals'.
-static void launch_accel_tracking(mh_ctx* c, int mode) {
-    if (c->nat == 0) return;
-    accel_tracking_backends()[c->size_class].eval(c, c->d_x, mode);
-}
-
-// The muscle-output goals' likewise, after the acceleration-tracking goals'.
-static void launch_muscle_outputs(mh_ctx* c, int mode) {
-    if (c->nmo == 0) return;
-    muscle_outputs_backends()[c->size_class].eval(c, c->d_x, mode);
-}
-
-// The metabolics goals' likewise, after the muscle-output goals'.
-static void launch_metabolics(mh_ctx* c, int mode) {
-    if (c->nmet == 0) return;
-    metabolics_backends()[c->size_class].eval(c, c->d_x, mode);
+// The lane-goal families' integrands (mode 0) and their gradient parts too
+// (mode 1), after the other goals' kernels, by the kernels of the context's
+// size class whatever back end serves g and J.  In this order: each family adds
+// to what the one before it left in grad / tpart, so the sums' bits depend on it.
+static void launch_lane_goals(mh_ctx* c, int mode) {
+    for (int f = 0; f < LG_COUNT; ++f)
+        if (c->lane_goals[f].ngoals) lane_goal_family(f).eval[c->size_class](c, c->d_x, mode);
 }
 
 // The objective (partial = false) or this shard's partial of it (partial =
@@ -3930,10 +3903,7 @@ static int eval_f_impl(mh_ctx* c, const double* x, double* f, bool partial) {
     Layout L = make_layout(c, 0, c->G);
     if (c->ngoals > 0) c->be->integrand(c, c->d_x);
     launch_marker_tracking(c, L, 0);   // after k_integrand: the marker-tracking goals' slots
-    launch_joint_reaction(c, 0);       // and the joint-reaction goals'
-    launch_accel_tracking(c, 0);       // and the acceleration-tracking goals'
-    launch_muscle_outputs(c, 0);       // and the muscle-output goals'
-    launch_metabolics(c, 0);           // and the metabolics goals'
+    launch_lane_goals(c, 0);           // and the lane-goal families'
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)
@@ -3967,10 +3937,7 @@ static int eval_grad_f_impl(mh_ctx* c, const double* x, double* grad, bool parti
         c->be->grad(c, c->d_x);
     }
     launch_marker_tracking(c, L, 1);   // after k_grad: adds to the coordinates' and the t0 / tf entries
-    launch_joint_reaction(c, 1);       // after both: adds to every direction's entry
-    launch_accel_tracking(c, 1);       // after the three: adds to its live directions' entries
-    launch_muscle_outputs(c, 1);       // after the four: adds to the entries of the inputs an output reads
-    launch_metabolics(c, 1);           // after the five: adds to the entries of the inputs its muscles read
+    launch_lane_goals(c, 1);           // after both: each family adds to its live directions' entries
     c->d_quad = quad;
     HIPCHK(hipGetLastError());
     if (c->has_marker && endpoint)   // after k_grad: adds to the final coordinates' entries
@@ -4008,10 +3975,7 @@ extern "C" int mh_eval_objective_terms(mh_ctx* c, const double* x, double* terms
     Layout L = make_layout(c, 0, c->G);
     c->be->integrand(c, c->d_x);
     launch_marker_tracking(c, L, 0);
-    launch_joint_reaction(c, 0);
-    launch_accel_tracking(c, 0);
-    launch_muscle_outputs(c, 0);
-    launch_metabolics(c, 0);
+    launch_lane_goals(c, 0);
     HIPCHK(hipGetLastError());
     if (c->has_marker)
         hipLaunchKernelGGL(k_marker_final, dim3((unsigned)c->ngoals), dim3(128), 0, c->stream, c->M, L, c->GS,
@@ -4032,23 +3996,43 @@ extern "C" int mh_eval_grad_f_partial(mh_ctx* c, const double* x, double* grad) 
     return eval_grad_f_impl(c, x, grad, true);
 }
 
+// A device allocation that is freed on scope exit, so that an early return
+// (HIPCHK) leaks nothing.
+struct DevBuf {
+    void* p = nullptr;
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes); }
+    template <class T>
+    T* as() const { return (T*)p; }
+};
+
+// One probe call on the context's stream: nin doubles of input rows to the
+// device, launch(din, dout), nout doubles of results back, one synchronisation.
+// A launch that returns a status ends the call with it.
+template <class F>
+static int run_probe(mh_ctx* c, const double* in, size_t nin, double* out, size_t nout, const F& launch) {
+    DevBuf din, dout;
+    HIPCHK(din.alloc(sizeof(double) * nin));
+    HIPCHK(dout.alloc(sizeof(double) * std::max<size_t>(nout, 1)));
+    HIPCHK(hipMemcpyAsync(din.p, in, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
+    (void)hipGetLastError();
+    const int rc = launch(din.as<const double>(), dout.as<double>());
+    if (rc) return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(out, dout.p, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    return MH_OK;
+}
+
 extern "C" int mh_eval_dae(mh_ctx* c, int32_t np, const double* inputs, double* outputs) {
     if (!c || !inputs || !outputs || np < 0) return set_err(MH_ERR_INVALID, "bad argument");
     if (np == 0) return MH_OK;
     HIPCHK(hipSetDevice(c->device));
-    double *din = nullptr, *dout = nullptr;
-    const size_t nin = (size_t)np * (1 + c->NI), nout = (size_t)np * c->NO;
-    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
-    HIPCHK(hipMalloc(&dout, sizeof(double) * std::max<size_t>(nout, 1)));
-    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
-    (void)hipGetLastError();
-    c->be->probe(c, np, din, dout);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(outputs, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    return MH_OK;
+    return run_probe(c, inputs, (size_t)np * (1 + c->NI), outputs, (size_t)np * c->NO,
+            [&](const double* din, double* dout) { c->be->probe(c, np, din, dout); return MH_OK; });
 }
 
 extern "C" int mh_eval_joint_reaction(mh_ctx* c, int32_t goal, int32_t np, const double* inputs, double* out) {
@@ -4058,19 +4042,8 @@ extern "C" int mh_eval_joint_reaction(mh_ctx* c, int32_t goal, int32_t np, const
         return set_err(MH_ERR_INVALID, "goal %d is not a joint reaction goal", goal);
     if (np == 0) return MH_OK;
     HIPCHK(hipSetDevice(c->device));
-    double *din = nullptr, *dout = nullptr;
-    const size_t nin = (size_t)np * (1 + c->NI), nout = (size_t)np * 6;
-    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
-    HIPCHK(hipMalloc(&dout, sizeof(double) * nout));
-    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
-    (void)hipGetLastError();
-    joint_reaction_backends()[c->size_class].probe(c, goal, np, din, dout);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    return MH_OK;
+    return run_probe(c, inputs, (size_t)np * (1 + c->NI), out, (size_t)np * 6,
+            [&](const double* din, double* dout) { joint_reaction_probe(c, goal, np, din, dout); return MH_OK; });
 }
 extern "C" int mh_eval_frame_accelerations(mh_ctx* c, int32_t goal, int32_t np, const double* inputs, double* out) {
     if (!c || !inputs || !out) return set_err(MH_ERR_INVALID, "bad argument");
@@ -4080,19 +4053,8 @@ extern "C" int mh_eval_frame_accelerations(mh_ctx* c, int32_t goal, int32_t np, 
     const int nf = c->goals[goal].term_count / 4;
     if (nf == 0) return MH_OK;
     HIPCHK(hipSetDevice(c->device));
-    double *din = nullptr, *dout = nullptr;
-    const size_t nin = (size_t)np * (1 + c->NI), nout = (size_t)np * nf * 3;
-    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
-    HIPCHK(hipMalloc(&dout, sizeof(double) * nout));
-    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
-    (void)hipGetLastError();
-    accel_tracking_backends()[c->size_class].probe(c, goal, np, din, dout);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    return MH_OK;
+    return run_probe(c, inputs, (size_t)np * (1 + c->NI), out, (size_t)np * nf * 3,
+            [&](const double* din, double* dout) { accel_tracking_probe(c, goal, np, din, dout); return MH_OK; });
 }
 extern "C" int mh_eval_muscle_outputs(mh_ctx* c, int32_t nout, const int32_t* muscle, const int32_t* output,
         int32_t np, const double* inputs, double* out) {
@@ -4107,24 +4069,16 @@ extern "C" int mh_eval_muscle_outputs(mh_ctx* c, int32_t nout, const int32_t* mu
             return set_err(MH_ERR_INVALID, "mh_eval_muscle_outputs: muscle output %d out of range", output[k]);
     }
     HIPCHK(hipSetDevice(c->device));
-    double *din = nullptr, *dout = nullptr;
-    int* dsel = nullptr;
-    const size_t nin = (size_t)np * (1 + c->NI), no = (size_t)np * nout;
-    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
-    HIPCHK(hipMalloc(&dout, sizeof(double) * no));
-    HIPCHK(hipMalloc(&dsel, sizeof(int) * 2 * (size_t)nout));
-    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
+    DevBuf sel;   // the muscles, then the outputs
+    HIPCHK(sel.alloc(sizeof(int) * 2 * (size_t)nout));
+    int* dsel = sel.as<int>();
     HIPCHK(hipMemcpyAsync(dsel, muscle, sizeof(int) * nout, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(dsel + nout, output, sizeof(int) * nout, hipMemcpyHostToDevice, c->stream));
-    (void)hipGetLastError();
-    muscle_outputs_backends()[c->size_class].probe(c, nout, dsel, dsel + nout, np, din, dout);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * no, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    (void)hipFree(dsel);
-    return MH_OK;
+    return run_probe(c, inputs, (size_t)np * (1 + c->NI), out, (size_t)np * nout,
+            [&](const double* din, double* dout) {
+                muscle_outputs_probe(c, nout, dsel, dsel + nout, np, din, dout);
+                return MH_OK;
+            });
 }
 
 extern "C" int mh_eval_metabolics(mh_ctx* c, int32_t nterms, const int32_t* index, const int32_t* column,
@@ -4137,27 +4091,18 @@ extern "C" int mh_eval_metabolics(mh_ctx* c, int32_t nterms, const int32_t* inde
         return set_err(MH_ERR_INVALID, "mh_eval_metabolics: %s", nterms < 0 ? "negative term count" : msg);
     const int nm = (nterms - MH_MET_HEADER) / MH_MET_PER_MUSCLE;
     HIPCHK(hipSetDevice(c->device));
-    double *din = nullptr, *dout = nullptr, *dw = nullptr;
-    int* dsel = nullptr;
-    const size_t nin = (size_t)np * (1 + c->NI), no = (size_t)np * (5 + nm);
-    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
-    HIPCHK(hipMalloc(&dout, sizeof(double) * no));
-    HIPCHK(hipMalloc(&dw, sizeof(double) * (size_t)nterms));
-    HIPCHK(hipMalloc(&dsel, sizeof(int) * 2 * (size_t)nterms));
-    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(dw, weight, sizeof(double) * nterms, hipMemcpyHostToDevice, c->stream));
+    DevBuf w, sel;   // the block's weights; its indices, then its columns
+    HIPCHK(w.alloc(sizeof(double) * (size_t)nterms));
+    HIPCHK(sel.alloc(sizeof(int) * 2 * (size_t)nterms));
+    int* dsel = sel.as<int>();
+    HIPCHK(hipMemcpyAsync(w.p, weight, sizeof(double) * nterms, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(dsel, index, sizeof(int) * nterms, hipMemcpyHostToDevice, c->stream));
     HIPCHK(hipMemcpyAsync(dsel + nterms, column, sizeof(int) * nterms, hipMemcpyHostToDevice, c->stream));
-    (void)hipGetLastError();
-    metabolics_backends()[c->size_class].probe(c, nm, dsel, dsel + nterms, dw, np, din, dout);
-    HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(out, dout, sizeof(double) * no, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    (void)hipFree(dw);
-    (void)hipFree(dsel);
-    return MH_OK;
+    return run_probe(c, inputs, (size_t)np * (1 + c->NI), out, (size_t)np * (5 + nm),
+            [&](const double* din, double* dout) {
+                metabolics_probe(c, nm, dsel, dsel + nterms, w.as<double>(), np, din, dout);
+                return MH_OK;
+            });
 }
 
 // Path-constraint values of np probe rows [t, states, controls, ...]
@@ -4191,19 +4136,8 @@ extern "C" int mh_eval_path(mh_ctx* c, int32_t np, const double* inputs, double*
     if (!c || !inputs || !outputs || np < 0) return set_err(MH_ERR_INVALID, "bad argument");
     if (np == 0 || c->npc == 0) return MH_OK;
     HIPCHK(hipSetDevice(c->device));
-    double *din = nullptr, *dout = nullptr;
-    const size_t nin = (size_t)np * (1 + c->NI), nout = (size_t)np * c->npc;
-    HIPCHK(hipMalloc(&din, sizeof(double) * nin));
-    HIPCHK(hipMalloc(&dout, sizeof(double) * nout));
-    HIPCHK(hipMemcpyAsync(din, inputs, sizeof(double) * nin, hipMemcpyHostToDevice, c->stream));
-    const int rc = path_probe(c, np, din, dout);
-    if (!rc) {
-        HIPCHK(hipMemcpyAsync(outputs, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-    }
-    (void)hipFree(din);
-    (void)hipFree(dout);
-    return rc;
+    return run_probe(c, inputs, (size_t)np * (1 + c->NI), outputs, (size_t)np * c->npc,
+            [&](const double* din, double* dout) { return path_probe(c, np, din, dout); });
 }
 
 // Endpoint-equation values of np probe rows [initial_time, initial inputs,

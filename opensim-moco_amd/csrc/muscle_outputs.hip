@@ -6,8 +6,8 @@
 // (dae_device.hpp).  No
 // Newton-Euler backward pass, no mass matrix, no dae_eval: the kernel works
 // with prescribed kinematics and costs a fraction of a dynamics lane.  One
-// instantiation per size class, selected by muscle_outputs_backends()
-// [size_class] whatever back end serves g and J.  A translation unit of its
+// instantiation per size class, selected by the context's whatever back end
+// serves g and J.  A translation unit of its
 // own, as joint_reaction.hip: generic.hip compiles to the code it had
 // without it.
 #include "mo_device.hpp"
@@ -40,8 +40,7 @@ __global__ void __launch_bounds__(64) k_muscle_outputs(DevModel M, Layout L, Lan
     if (g < 0) return;
     const int tb = GS.goals[g].term_begin, im = GS.gidx[tb], which = GS.gcol[tb];
     if (!base && !mo_live(M, im, which, dir)) return;
-    MoIn in{x + 2 + (long)k * L.NS, x + 2 + (long)L.NS * L.G + (long)k * L.NC, x + L.DB + (long)k * L.NDV, L.NS, L.NC,
-            -1, 0.0};
+    PointIn in = point_in(L, x, k);
     const double t = lane_time(Ln, grid[k], x[0], x[1], r, in.pi, in.step);
     Pose X[Z::MB + 1];
     SV V[Z::MB + 1];
@@ -55,46 +54,18 @@ __global__ void __launch_bounds__(64) k_muscle_outputs(DevModel M, Layout L, Lan
     });
 }
 
-// One thread per (grid point, direction): the quotients of k_muscle_outputs'
-// lane values with k_grad's formulas and arithmetic, G.weight * dur * quad[k]
-// * dL of the goals the direction is live for, added to what the other goal
-// kernels left in grad / tpart (after them on the same stream: one writer per
-// entry and launch); direction 0 also writes the goals' integrand slots of C.
-// A direction live for no goal writes nothing: its entry keeps its bits.
-__global__ void __launch_bounds__(64) k_muscle_outputs_grad(DevModel M, Layout L, Lanes Ln, GoalSet GS, int nmo,
-        const double* __restrict__ x, const double* __restrict__ quad, const double* __restrict__ lv,
-        double* __restrict__ C, double* __restrict__ grad, double* __restrict__ tpart) {
-#pragma clang fp contract(off)
-    const int ND = Ln.ND;
-    const long tid = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (tid >= (long)L.G * ND) return;
-    const int k = (int)(tid / ND), d = (int)(tid % ND);
-    const double dur = x[1] - x[0], h = Ln.h;
-    const double* lk = lv + (long)k * Ln.stride * nmo;
-    double acc = 0.0;
-    bool any = false;
-    int j = 0;
-    for (int g = 0; g < GS.ngoals && j < nmo; ++g) {
-        const mh_goal G = GS.goals[g];
-        if (G.kind != MH_GOAL_OUTPUT) continue;
-        const int tb = G.term_begin;
-        if (mo_live(M, GS.gidx[tb], GS.gcol[tb], d)) {
-            const double l0 = lk[(long)Ln.base * nmo + j], l1 = lk[(long)d * nmo + j];
-            const double dL = Ln.fd == MH_FD_CENTRAL ? (l1 - lk[(long)(ND + d) * nmo + j]) / (2.0 * h)
-                            : (Ln.fd == MH_FD_FORWARD ? (l1 - l0) / h : (l0 - l1) / h);
-            acc += G.weight * dur * quad[k] * dL;
-            any = true;
-            if (d == 0) C[(long)k * GS.ngoals + g] = quad[k] * l0;
-        }
-        ++j;
+// The family's part of k_lane_goal_grad (goal_lanes.hpp): a direction is live
+// for a goal where k_muscle_outputs evaluated its lane (mo_live).
+struct MuscleOutputGoals : OneEntryPerGoal {
+    static constexpr int kind = MH_GOAL_OUTPUT;
+    struct Args {
+        DevModel M;
+    };
+    __device__ static bool live(const Args& A, const GoalSet& GS, int g, int d) {
+        const int tb = GS.goals[g].term_begin;
+        return mo_live(A.M, GS.gidx[tb], GS.gcol[tb], d);
     }
-    if (!any) return;
-    if (d < 2) tpart[(long)k * 2 + d] += acc;
-    else if (d - 2 < L.NS) grad[2 + (long)k * L.NS + (d - 2)] += acc;
-    else if (d - 2 < L.NS + L.NC) grad[2 + (long)L.NS * L.G + (long)k * L.NC + (d - 2 - L.NS)] += acc;
-    else if (d - 2 < L.NS + L.NC + L.NDV) grad[L.DB + (long)k * L.NDV + (d - 2 - L.NS - L.NC)] += acc;
-    else grad[L.XM + (long)k * L.NM + (d - 2 - L.NS - L.NC - L.NDV)] += acc;
-}
+};
 
 // mh_eval_muscle_outputs: one thread per input row [time, NI point inputs],
 // output which[o] of muscle mus[o] to outp[row nout + o]; one kinematic pass
@@ -106,7 +77,7 @@ __global__ void __launch_bounds__(64) k_muscle_outputs_probe(DevModel M, Layout 
     const int p = blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= npts) return;
     const double* row = inp + (long)p * (1 + L.NI);
-    const MoIn in{row + 1, row + 1 + L.NS, row + 1 + L.NS + L.NC, L.NS, L.NC, -1, 0.0};
+    const PointIn in{row + 1, row + 1 + L.NS, row + 1 + L.NS + L.NC, L.NS, L.NC, -1, 0.0};
     unsigned long long mask = 0ull;
     for (int o = 0; o < nout; ++o) mask |= mo_muscle_bodies(M, mus[o]);
     Pose X[Z::MB + 1];
@@ -126,20 +97,14 @@ __global__ void __launch_bounds__(64) k_muscle_outputs_probe(DevModel M, Layout 
 
 template <class Z>
 static void be_muscle_outputs(mh_ctx* c, const double* x, int mode) {
-    Layout L = make_layout(c, 0, c->G);
-    if (mode == 0) {
-        // base lanes only
-        const Lanes ln{c->fd, c->lanes_mo.ND, 1, 0, c->h};
-        hipLaunchKernelGGL(k_muscle_outputs<Z>, dim3((unsigned)(((long)c->G * c->nmo + 63) / 64)), dim3(64), 0,
-                c->stream, c->M, L, ln, c->GS, c->nmo, x, c->d_grid, c->d_quad, c->d_C, c->d_mo);
-        return;
-    }
-    const Lanes& ln = c->lanes_mo;
-    const long lanes = (long)c->G * ln.stride, dirs = (long)c->G * ln.ND;
-    hipLaunchKernelGGL(k_muscle_outputs<Z>, dim3((unsigned)((lanes * c->nmo + 63) / 64)), dim3(64), 0, c->stream, c->M,
-            L, ln, c->GS, c->nmo, x, c->d_grid, c->d_quad, (double*)nullptr, c->d_mo);
-    hipLaunchKernelGGL(k_muscle_outputs_grad, dim3((unsigned)((dirs + 63) / 64)), dim3(64), 0, c->stream, c->M, L,
-            ln, c->GS, c->nmo, x, c->d_quad, c->d_mo, c->d_C, c->d_grad, c->d_tpart);
+    const LaneGoals& R = c->lane_goals[LG_MUSCLE_OUTPUTS];
+    launch_lane_goal_family<MuscleOutputGoals>(c, LG_MUSCLE_OUTPUTS, {c->M}, x, mode,
+            [&](const Layout& L, const Lanes& ln, int mode) {
+                const long threads = (long)c->G * ln.stride * R.entries;
+                hipLaunchKernelGGL(k_muscle_outputs<Z>, dim3((unsigned)((threads + 63) / 64)), dim3(64), 0, c->stream,
+                        c->M, L, ln, c->GS, R.entries, x, c->d_grid, c->d_quad, mode ? (double*)nullptr : c->d_C,
+                        R.lv);
+            });
 }
 template <class Z>
 static void be_muscle_outputs_probe(mh_ctx* c, int nout, const int* mus, const int* which, int np,
@@ -149,12 +114,17 @@ static void be_muscle_outputs_probe(mh_ctx* c, int nout, const int* mus, const i
             which, np, in, out);
 }
 
-const MuscleOutputsBackend* muscle_outputs_backends() {
-    static const MuscleOutputsBackend kMuscleOutputs[4] = {
-        {&be_muscle_outputs<SzSmall>, &be_muscle_outputs_probe<SzSmall>},
-        {&be_muscle_outputs<SzMedium>, &be_muscle_outputs_probe<SzMedium>},
-        {&be_muscle_outputs<SzLarge>, &be_muscle_outputs_probe<SzLarge>},
-        {&be_muscle_outputs<SzBody>, &be_muscle_outputs_probe<SzBody>},
-    };
-    return kMuscleOutputs;
+const LaneGoalFamily& muscle_output_goals() {
+    static const LaneGoalFamily kFamily = {
+        MuscleOutputGoals::kind,
+        {&be_muscle_outputs<SzSmall>, &be_muscle_outputs<SzMedium>, &be_muscle_outputs<SzLarge>,
+         &be_muscle_outputs<SzBody>}};
+    return kFamily;
+}
+void muscle_outputs_probe(mh_ctx* c, int nout, const int* mus, const int* which, int np, const double* in,
+        double* out) {
+    static constexpr decltype(&be_muscle_outputs_probe<SzSmall>) kProbe[4] = {
+        &be_muscle_outputs_probe<SzSmall>, &be_muscle_outputs_probe<SzMedium>, &be_muscle_outputs_probe<SzLarge>,
+        &be_muscle_outputs_probe<SzBody>};
+    kProbe[c->size_class](c, nout, mus, which, np, in, out);
 }

@@ -1,5 +1,5 @@
 """MocoAccelerationTrackingGoal on the dynamics-stage lanes (include/mocohip.h
-MH_GOAL_ACCELERATION_TRACKING; k_accel_tracking, k_accel_tracking_grad,
+MH_GOAL_ACCELERATION_TRACKING; k_accel_tracking, k_lane_goal_grad,
 mh_eval_frame_accelerations).
 
 The checker is a NumPy restatement built on test_joint_reaction.body_motion

@@ -1,6 +1,6 @@
 """MocoJointReactionGoal on the dynamics stage of the generic interpreter
 (include/mocohip.h MH_GOAL_JOINT_REACTION; k_joint_reaction,
-k_joint_reaction_grad, mh_eval_joint_reaction).
+k_lane_goal_grad, mh_eval_joint_reaction).
 
 The checker is a NumPy Newton-Euler and momentum restatement built on
 tests/test_frame_distance.forward_kinematics: from (t, q, u, udot) every body's

@@ -540,7 +540,7 @@ def _coupled_muscle_study(dynamics, with_goal):
 @pytest.mark.parametrize("dynamics", ["explicit", "implicit"])
 def test_untouched_multiplier_slack_and_acceleration_entries(dynamics):
     """A problem with kinematic constraints: the multiplier directions have
-    lanes (ND = NI - NSL + 2) and k_muscle_outputs_grad a branch that writes
+    lanes (ND = NI - NSL + 2) and k_lane_goal_grad a branch that writes
     their entries, so they are where a wrong write would land.  The multiplier,
     slack and (implicit dynamics) acceleration entries of grad f carry the bits
     of the problem without the goal, where the multiplier goal has written

@@ -460,3 +460,95 @@ def test_device_shard_partials_against_reference(fd):
 @pytest.mark.gpu
 def test_bounds_reject_mutations_of_the_reference_device():
     _check_sensitivity("device", HipNLP)
+
+
+# ---- the four lane-goal families on one problem (GPU) -------------------------
+
+def _four_family_study(fd, kinds):
+    """The coupled double pendulum with a muscle (test_muscle_outputs'
+    _coupled_muscle_study: Hermite-Simpson, N = 2, implicit dynamics, so that
+    the input has coordinates, speeds, a muscle state, a control, acceleration
+    variables, multipliers at every grid point and slacks at the midpoints)
+    with one goal of each kind in ``kinds`` in front of its effort goal, in the
+    families' launch order: joint reaction (14), acceleration tracking (15),
+    muscle output (17), metabolics (18)."""
+    from mocohip.problem import MocoJointReactionGoal, MocoOutputGoal
+    from test_acceleration_tracking import _with_goal
+    from test_metabolics import _with_metabolics
+    from test_muscle_outputs import _coupled_muscle_study
+    st = _coupled_muscle_study("implicit", False)
+    st.solver.optim_finite_difference_scheme = fd
+    base = list(st.problem.goals)
+    st.problem.goals = []
+    if 14 in kinds:
+        st.problem.add_goal(MocoJointReactionGoal("reaction", 0.5, joint_path="j1", loads_frame="child"))
+    if 15 in kinds:
+        sw = configs.double_pendulum_swing_states()
+        _with_goal(st, "accel", 0.75, ["/bodyset/b1", "/bodyset/b0"], sw.times,
+                   {"q0": sw.columns["/jointset/j0/q0/value"], "q1": sw.columns["/jointset/j1/q1/value"]})
+    if 17 in kinds:
+        st.problem.add_goal(MocoOutputGoal("output", 1.5, output_path="/forceset/flexor|tendon_force"))
+    if 18 in kinds:
+        _with_metabolics(st, "/forceset/flexor")   # (inserts its goal "met" in front)
+        st.problem.goals.append(st.problem.goals.pop(0))
+    st.problem.goals += base
+    return st
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("fd", FDS)
+def test_four_lane_goal_families_together(fd):
+    """One goal of each of kinds 14, 15, 17 and 18 on one problem, whose
+    directions go down every branch of grad_entry (t0 / tf, states, controls,
+    acceleration variables, multipliers) and whose slacks have no lane.  Each
+    goal's objective term has the bits it has in the study holding that goal
+    alone; grad f equals the gradient without the four plus the four separate
+    contributions within the bound of test_acceleration_tracking's
+    test_two_goals_and_kinds_12_14_15_together (8 eps on the summands'
+    magnitudes plus 1e-12 |grad|); every family's contribution is non-zero
+    somewhere; the slack entries, and every entry no family moves on its own,
+    carry the bits of the study without the four."""
+    kinds = (14, 15, 17, 18)
+    names = {14: "reaction", 15: "accel", 17: "output", 18: "met"}
+    runs, x = {}, None
+    for key in (kinds, *((k,) for k in kinds), ()):
+        st = _four_family_study(fd, key)
+        nlp = HipNLP(st.problem.create_rep(), st.solver.options())
+        if x is None:
+            G, NS = nlp.G, nlp.NS
+            r = np.random.default_rng(12)
+            x = nlp.random_iterate(r.uniform(-1, 1, nlp.n))
+            x[0], x[1] = 0.1, 0.9
+            x[2:2 + NS * G].reshape(G, NS)[:, 4:] = r.uniform(0.2, 0.8, (G, NS - 4))   # activations
+            N = nlp.opts.num_mesh_intervals
+            XM = 2 + (NS + nlp.NC) * G
+            XL = XM + nlp.NM * G
+            DB = XL + nlp.NSL * N
+            assert nlp.NM * G > 0 and nlp.NSL * N > 0 and nlp.NDV * G > 0 and DB + nlp.NDV * G == nlp.n
+        assert nlp.n == len(x)
+        goal_names = [g.name for g in st.problem.goals]
+        runs[key] = (dict(zip(goal_names, nlp.objective_terms(x))), nlp.eval_grad_f(x))
+        nlp.close()
+    terms, g_all = runs[kinds]
+    g_0 = runs[()][1]
+    assert list(terms)[:4] == [names[k] for k in kinds]
+    for k in kinds:
+        alone = runs[(k,)][0][names[k]]
+        assert alone != 0.0 and np.float64(terms[names[k]]).tobytes() == np.float64(alone).tobytes(), (k, fd)
+    parts = [runs[(k,)][1] - g_0 for k in kinds]
+    want, mag = g_0.copy(), np.abs(g_0)
+    for p in parts:
+        want = want + p
+        mag = mag + np.abs(p)
+    assert (np.abs(g_all - want) <= 8 * EPS * mag + 1e-12 * np.abs(g_all)).all()
+    for p in parts:
+        assert np.abs(p).max() > 0
+    still = np.ones(len(x), bool)
+    for k in kinds:
+        still &= runs[(k,)][1].view(np.uint64) == g_0.view(np.uint64)
+    assert still[XL:DB].all()   # the slacks: no lane in any family
+    assert g_all[still].tobytes() == g_0[still].tobytes()
+    # t0, tf, states or controls, and the acceleration variables do move; no goal reads the multipliers,
+    # whose entries hold the multiplier term's non-zero values, so a stray write there would show
+    assert not still[[0, 1]].any() and not still[2:XM].all() and not still[DB:].all()
+    assert (g_0[XM:XL] != 0.0).all()
