@@ -174,14 +174,35 @@ typedef struct mh_table {
     int32_t reserved;
 } mh_table;
 
-/* OpenSim ExternalForce with force and point expressed in ground. */
+/* OpenSim ExternalForce with force and point expressed in ground (kind 0),
+ * or a station-plane ground contact force (kinds 1..3: the reference's
+ * StationPlaneContactForce.h): a station fixed in `body` against the ground
+ * plane y = 0, the force (fx, fy, 0) on the body at the station from the
+ * station's height, normal velocity and ground-x sliding velocity (friction
+ * acts along ground x only, as in the reference).  A contact record has
+ * table = point_col = torque_col = -1 and force_col = the offset into
+ * mh_model.table_coefs of MH_CONTACT_PARAMS doubles: station location in the
+ * body (3), stiffness, dissipation, friction coefficient (MeyerFregly2016: 1,
+ * unused), tangent velocity scaling factor (> 0; MeyerFregly2016: unused),
+ * depth_offset (EspositoMiller2018, >= 0) / tscale (MeyerFregly2016) / 0.
+ * Contact records follow all table-driven records, their parameter blocks
+ * follow all table coefficients (ncoefs counts them), both in the order the
+ * forces were added.  Contact runs on the generic interpreter only and not
+ * with prescribed kinematics (MH_ERR_UNSUPPORTED). */
+enum mh_external_kind {
+    MH_EXT_TABLE = 0,
+    MH_EXT_CONTACT_ACKERMANN_VAN_DEN_BOGERT = 1,
+    MH_EXT_CONTACT_ESPOSITO_MILLER = 2,
+    MH_EXT_CONTACT_MEYER_FREGLY = 3
+};
+#define MH_CONTACT_PARAMS 8
 typedef struct mh_external_force {
     int32_t body;
     int32_t table;
     int32_t force_col;   /* first of 3 columns, -1 = none                  */
     int32_t point_col;   /* first of 3 columns, -1 = body origin           */
     int32_t torque_col;  /* first of 3 columns, -1 = none                  */
-    int32_t reserved;
+    int32_t kind;        /* mh_external_kind                               */
 } mh_external_force;
 
 /* Kinematic constraints (CasOCTranscription.cpp:298-333,
@@ -1236,6 +1257,16 @@ int mh_eval_muscle_outputs(mh_ctx* ctx, int32_t nout, const int32_t* muscle, con
  * Synchronous. */
 int mh_eval_metabolics(mh_ctx* ctx, int32_t nterms, const int32_t* index, const int32_t* column,
         const double* weight, int32_t npoints, const double* inputs, double* out);
+/* The model's station-plane contact forces (mh_external_force records of
+ * kind 1..3, in record order) at npoints rows [time, point inputs] as for
+ * mh_eval_dae: out[npoints][ncontacts][9] = the force on the body at the
+ * station, in ground (3), the station's position in ground (3) and its
+ * velocity in ground (3).  A velocity-stage kernel (k_contact_forces) over the
+ * bodies that carry a station, with the force function dae_eval calls; no
+ * dynamics run.  npoints <= 0: MH_ERR_INVALID; a model without contact: MH_OK,
+ * nothing written; a problem with MocoParameters: MH_ERR_UNSUPPORTED.
+ * Synchronous. */
+int mh_eval_contact_forces(mh_ctx* ctx, int32_t npoints, const double* inputs, double* out);
 /* Path-constraint probe, the counterpart of mh_eval_dae for the path
  * callback: the npath path-equation values of npoints probe rows [time, point
  * inputs (NS + NC + NDV + ...)] (the row of mh_get_callback_sparsity, W

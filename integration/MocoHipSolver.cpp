@@ -48,6 +48,8 @@
 #include <OpenSim/Moco/MocoProblemRep.h>
 #include <OpenSim/Moco/MocoUtilities.h>
 #include <OpenSim/Simulation/Model/ExternalForce.h>
+#include <OpenSim/Simulation/Model/Station.h>
+#include <Moco/Components/StationPlaneContactForce.h>
 #include <OpenSim/Simulation/Model/Model.h>
 #include <OpenSim/Simulation/Model/PhysicalOffsetFrame.h>
 #include <OpenSim/Simulation/SimbodyEngine/CoordinateCouplerConstraint.h>
@@ -368,6 +370,45 @@ void compileModel(const Model& model, mhb::Problem& prob) {
         he.point_identifier = ef.get_point_identifier();
         he.torque_identifier = ef.get_torque_identifier();
         m.add_external_force(he);
+    }
+    // station-plane contact forces (StationPlaneContactForce.h): the station
+    // and the class's properties, in component-list order; mh_create runs
+    // them on the generic interpreter (the plane is ground y = 0, friction
+    // along ground x, as in the reference).  SmoothSphereHalfSpaceForce is not
+    // a StationPlaneContactForce and stays refused with every other force.
+    for (const StationPlaneContactForce& cf : model.getComponentList<StationPlaneContactForce>()) {
+        if (!cf.get_appliesForce()) continue;
+        const auto& st = cf.getConnectee<Station>("station");
+        mhb::Station hs;
+        hs.name = st.getName();
+        hs.path = st.getAbsolutePathString();
+        hs.body = st.getParentFrame().findBaseFrame().getName();
+        const SimTK::Vec3 loc = st.getParentFrame().findTransformInBaseFrame() * st.get_location();
+        for (int d = 0; d < 3; ++d) hs.location[d] = loc[d];
+        m.add_station(hs);
+        mhb::ContactForce hc;
+        hc.name = cf.getName();
+        hc.path = cf.getAbsolutePathString();
+        hc.station = hs.path;
+        if (const auto* a = dynamic_cast<const AckermannVanDenBogert2010Force*>(&cf)) {
+            hc.kind = MH_EXT_CONTACT_ACKERMANN_VAN_DEN_BOGERT;
+            const double p[5] = {a->get_stiffness(), a->get_dissipation(), a->get_friction_coefficient(),
+                    a->get_tangent_velocity_scaling_factor(), 0.0};
+            std::copy(p, p + 5, hc.params);
+        } else if (const auto* e = dynamic_cast<const EspositoMiller2018Force*>(&cf)) {
+            hc.kind = MH_EXT_CONTACT_ESPOSITO_MILLER;
+            const double p[5] = {e->get_stiffness(), e->get_dissipation(), e->get_friction_coefficient(),
+                    e->get_tangent_velocity_scaling_factor(), e->get_depth_offset()};
+            std::copy(p, p + 5, hc.params);
+        } else if (const auto* f = dynamic_cast<const MeyerFregly2016Force*>(&cf)) {
+            hc.kind = MH_EXT_CONTACT_MEYER_FREGLY;   // friction coefficient 1, latch velocity 0.05: fixed there
+            const double p[5] = {f->get_stiffness(), f->get_dissipation(), 1.0, 0.05, f->get_tscale()};
+            std::copy(p, p + 5, hc.params);
+        } else {
+            OPENSIM_THROW(Exception, "MocoHipSolver: StationPlaneContactForce '{}' of class {} is not supported",
+                    cf.getName(), cf.getConcreteClassName());
+        }
+        m.add_contact_force(hc);
     }
     for (const Marker& mk : model.getComponentList<Marker>()) {
         mhb::Marker hm;

@@ -2497,6 +2497,7 @@ struct mh_ctx {
     int n_lane_main = 0;
     int* d_par_lanes = nullptr;        // the lane of copy cp (cp >= 1) at [cp - 1]
     int nsprings = 0;
+    int ncontacts = 0;   // station-plane contact records (the last of the model's external forces)
     std::vector<mh_endpoint_equation> ep;
     std::vector<TplEntry> eptpl;       // row = equation, dir = endpoint input index
     std::vector<uint8_t> sp_ep;        // detected [equation][2 (1 + NI)] (empty: dense)
@@ -3100,6 +3101,8 @@ void muscle_outputs_probe(mh_ctx*, int nout, const int* mus, const int* which, i
         double* out);
 void metabolics_probe(mh_ctx*, int nm, const int* idx, const int* col, const double* w, int np, const double* in,
         double* out);
+// The rows of mh_eval_contact_forces (contact.hip): 9 values per contact record.
+void contact_forces_probe(mh_ctx*, int np, const double* in, double* out);
 // A metabolics term block (include/mocohip.h MH_GOAL_METABOLICS): six header
 // terms, then six per muscle.
 #define MH_MET_HEADER 6

@@ -7,7 +7,8 @@
 //   * GeometryPath with Conditional/Moving path points; tension applied as
 //     point forces; MovingPathPoint generalized-force terms;
 //   * DeGrooteFregly2016Muscle (DeGrooteFregly2016Muscle.cpp:186-425);
-//   * ExternalForce from piecewise-polynomial tables; CoordinateActuators.
+//   * ExternalForce from piecewise-polynomial tables; CoordinateActuators;
+//   * station-plane ground contact forces (contact_device.hpp).
 // All arithmetic is FP64 VALU.  Size classes (template parameters) bound the
 // per-lane arrays so that small models stay in VGPRs and large ones spill to
 // scratch with a lane-interleaved (coalesced) layout.
@@ -16,6 +17,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/mocohip.h"
+#include "contact_device.hpp"
 
 namespace mh {
 
@@ -1100,6 +1102,20 @@ __device__ void dae_eval(const DevModel& M, Work<MB, MQ, MP>& w, double time, co
     for (int ie = 0; ie < M.next; ++ie) {
         const mh_external_force E = M.ext[ie];
         const int bs = E.body + 1;
+        if (E.kind != MH_EXT_TABLE) {
+            // station-plane contact: the force at the station on the body (the
+            // opposite force acts on ground, which does not move)
+            const double* cp = M.coef + E.force_col;
+            const SV& Vb = w.V[bs];
+            double P[3], Vs[3], fx, fy, n0, n1, n2;
+            contact_station(w.X[bs].R, w.X[bs].p, Vb.w0, Vb.w1, Vb.w2, Vb.v0, Vb.v1, Vb.v2, cp, P, Vs);
+            contact_force(E.kind, cp, P[1], Vs[1], Vs[0], fx, fy);
+            cross3(P[0], P[1], P[2], fx, fy, 0.0, n0, n1, n2);
+            SV& Fb = w.F[bs];
+            Fb.w0 -= n0; Fb.w1 -= n1; Fb.w2 -= n2;
+            Fb.v0 -= fx; Fb.v1 -= fy;
+            continue;
+        }
         double F0 = 0, F1 = 0, F2 = 0, T0 = 0, T1 = 0, T2 = 0;
         double P0 = w.X[bs].p[0], P1 = w.X[bs].p[1], P2 = w.X[bs].p[2];
         if (E.force_col >= 0) {

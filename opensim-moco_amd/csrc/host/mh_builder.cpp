@@ -81,6 +81,33 @@ void Model::add_spring(SpringGeneralizedForce f) {
     if (f.path.empty()) f.path = "/forceset/" + f.name;
     springs.push_back(std::move(f));
 }
+void Model::add_station(Station s) {
+    if (!body(s.body)) fail("station '" + s.name + "': no body '" + s.body + "'");
+    if (s.path.empty()) s.path = "/" + s.name;
+    for (auto& x : stations)
+        if (x.path == s.path) { x = std::move(s); return; }
+    stations.push_back(std::move(s));
+}
+const Station* Model::find_station(const std::string& path) const {
+    for (auto& s : stations)
+        if (path == s.path || path == s.name || path == "/componentset/" + s.name ||
+                path == "/bodyset/" + s.body + "/" + s.name)
+            return &s;
+    return nullptr;
+}
+void Model::add_contact_force(ContactForce f) {
+    if (f.kind < MH_EXT_CONTACT_ACKERMANN_VAN_DEN_BOGERT || f.kind > MH_EXT_CONTACT_MEYER_FREGLY)
+        fail("contact force '" + f.name + "': unknown kind " + std::to_string(f.kind));
+    if (!find_station(f.station)) fail("contact force '" + f.name + "': no station '" + f.station + "' in the model");
+    for (auto& x : contact_forces)
+        if (x.name == f.name) fail("contact force name '" + f.name + "' is used twice");
+    if (f.kind != MH_EXT_CONTACT_MEYER_FREGLY && !(f.params[3] > 0.0))
+        fail("contact force '" + f.name + "': tangent_velocity_scaling_factor is not positive");
+    if (f.kind == MH_EXT_CONTACT_ESPOSITO_MILLER && !(f.params[4] >= 0.0))
+        fail("contact force '" + f.name + "': depth_offset is negative");
+    if (f.path.empty()) f.path = "/forceset/" + f.name;
+    contact_forces.push_back(std::move(f));
+}
 void Model::add_offset_frame(OffsetFrame f) {
     if (f.body != "ground" && !body(f.body)) fail("offset frame '" + f.name + "': no body '" + f.body + "'");
     if (f.path.empty()) f.path = (f.body == "ground" ? "/ground/" : "/bodyset/" + f.body + "/") + f.name;
@@ -379,6 +406,20 @@ void compile_model(const Model& M, const std::vector<Table>& extra_tables, Compi
         es.force_col = col3(e.force_identifier);
         es.point_col = col3(e.point_identifier);
         es.torque_col = col3(e.torque_identifier);
+        C.external.push_back(es);
+    }
+    // station-plane contact forces: records after the table-driven ones,
+    // parameter blocks after all table coefficients (include/mocohip.h)
+    for (auto& f : M.contact_forces) {
+        const Station* st = M.find_station(f.station);
+        if (!st) fail("contact force " + f.name + ": no station '" + f.station + "' in the model");
+        mh_external_force es{};
+        es.body = C.index_of_body(st->body);
+        es.table = es.point_col = es.torque_col = -1;
+        es.force_col = (int)C.coefs.size();
+        es.kind = f.kind;
+        C.coefs.insert(C.coefs.end(), st->location, st->location + 3);
+        C.coefs.insert(C.coefs.end(), f.params, f.params + 5);
         C.external.push_back(es);
     }
     // kinematic constraints: their functions after every other function
@@ -1616,6 +1657,21 @@ void read_description(const std::string& path, Problem& P, SolverSettings& S) {
             e.point_identifier = t.s();
             e.torque_identifier = t.s();
             M.add_external_force(e);
+        } else if (rec == "station") {
+            Station st;
+            st.name = t.s();
+            st.body = t.s();
+            t.d3(st.location);
+            st.path = t.s();
+            M.add_station(st);
+        } else if (rec == "contact") {
+            ContactForce f;
+            f.kind = t.i();
+            f.name = t.s();
+            f.station = t.s();
+            f.path = t.s();
+            for (double& v : f.params) v = t.d();
+            M.add_contact_force(f);
         } else if (rec == "problem") {
             P.time_initial = read_bounds(t);
             P.time_final = read_bounds(t);

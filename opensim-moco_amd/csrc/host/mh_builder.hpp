@@ -5,7 +5,8 @@
 // call mh_create: a plain C++ description of bodies, joints and their
 // coordinates, DeGrooteFregly2016 muscles with their GeometryPath (fixed /
 // conditional / moving path points, PathWraps over WrapCylinders),
-// CoordinateActuators, ExternalForces on data tables, CoordinateCoupler
+// CoordinateActuators, ExternalForces on data tables, station-plane contact
+// forces, CoordinateCoupler
 // constraints and markers, plus the problem's goals, bounds and path
 // constraints, lowered with the reference's rules:
 //   * coordinate order = Simbody's mobilized-body order (the multibody graph
@@ -160,6 +161,20 @@ struct ExternalForce {
     std::string force_identifier, point_identifier, torque_identifier;   // empty: none
 };
 
+// A body-fixed point, and a station-plane ground contact force on one
+// (include/mocohip.h mh_external_kind 1..3): params = stiffness, dissipation,
+// friction coefficient, tangent velocity scaling factor, depth_offset / tscale
+// / 0, as the record's parameter block carries them after the location.
+struct Station {
+    std::string name, body, path;
+    double location[3] = {0, 0, 0};
+};
+struct ContactForce {
+    int kind = MH_EXT_CONTACT_ACKERMANN_VAN_DEN_BOGERT;
+    std::string name, station, path;
+    double params[5] = {0, 0, 0, 0, 0};
+};
+
 struct CoordinateCoupler {
     std::string name, dependent;
     Function function;
@@ -183,6 +198,8 @@ public:
     std::vector<WrapCylinder> wraps;
     std::vector<SpringGeneralizedForce> springs;
     std::vector<OffsetFrame> offset_frames;
+    std::vector<Station> stations;
+    std::vector<ContactForce> contact_forces;   // in the order added
 
     void add_offset_frame(OffsetFrame f);
     // (body name or "ground", location in that body) of the Frame at path:
@@ -200,6 +217,11 @@ public:
     void add_constraint(const CoordinateCoupler& k) { constraints.push_back(k); }
     void add_wrap(const WrapCylinder& w) { wraps.push_back(w); }
     void add_spring(SpringGeneralizedForce f);
+    void add_station(Station s);
+    // the station a contact force names: by path, name, /componentset/<name>
+    // or /bodyset/<body>/<name>; null when there is none
+    const Station* find_station(const std::string& path) const;
+    void add_contact_force(ContactForce f);
 
     std::vector<const Joint*> tree_order() const;
     std::vector<const Coordinate*> coordinates() const;

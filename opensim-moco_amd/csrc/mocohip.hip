@@ -2098,8 +2098,30 @@ static int validate_and_layout(mh_ctx* c, const mh_problem* p, const mh_options*
     }
     for (int e = 0; e < M.nexternal; ++e) {
         const mh_external_force& E = M.external[e];
-        if (E.body < 0 || E.body >= M.nbodies || E.table < 0 || E.table >= M.ntables)
-            return set_err(MH_ERR_INVALID, "external force %d: bad body/table", e);
+        if (E.kind == MH_EXT_TABLE) {
+            if (c->ncontacts > 0)
+                return set_err(MH_ERR_INVALID, "external force %d: a table-driven force after a contact force", e);
+            if (E.body < 0 || E.body >= M.nbodies || E.table < 0 || E.table >= M.ntables)
+                return set_err(MH_ERR_INVALID, "external force %d: bad body/table", e);
+            continue;
+        }
+        // station-plane contact (include/mocohip.h mh_external_kind)
+        if (E.kind < MH_EXT_CONTACT_ACKERMANN_VAN_DEN_BOGERT || E.kind > MH_EXT_CONTACT_MEYER_FREGLY)
+            return set_err(MH_ERR_INVALID, "external force %d: unknown kind %d", e, E.kind);
+        if (E.table >= 0) return set_err(MH_ERR_INVALID, "contact force %d: kind %d with a table", e, E.kind);
+        if (E.body < 0 || E.body >= M.nbodies) return set_err(MH_ERR_INVALID, "contact force %d: bad body", e);
+        if (E.force_col < 0 || (int64_t)E.force_col + MH_CONTACT_PARAMS > M.ncoefs || !M.table_coefs)
+            return set_err(MH_ERR_INVALID, "contact force %d: parameters at %d are outside table_coefs", e,
+                    E.force_col);
+        const double* cp = M.table_coefs + E.force_col;
+        if (E.kind != MH_EXT_CONTACT_MEYER_FREGLY && !(cp[6] > 0.0))
+            return set_err(MH_ERR_INVALID, "contact force %d: tangent velocity scaling factor %g is not positive",
+                    e, cp[6]);
+        if (E.kind == MH_EXT_CONTACT_ESPOSITO_MILLER && !(cp[7] >= 0.0))
+            return set_err(MH_ERR_INVALID, "contact force %d: negative depth_offset %g", e, cp[7]);
+        if (c->presc)
+            return set_err(MH_ERR_UNSUPPORTED, "contact force %d: contact with prescribed kinematics", e);
+        ++c->ncontacts;
     }
     // SpringGeneralizedForce elements (ABI v8)
     if (M.nsprings < 0 || (M.nsprings > 0 && !M.springs)) return set_err(MH_ERR_INVALID, "bad springs");
@@ -2229,7 +2251,13 @@ static uint64_t model_hash(const mh_model* M) {
     h = fnv1a(h, M->actuators, sizeof(mh_actuator) * (size_t)M->nactuators);
     h = fnv1a(h, M->external, sizeof(mh_external_force) * (size_t)M->nexternal);
     for (int e = 0; e < M->nexternal; ++e) {
-        const int t = M->external[e].table;
+        const mh_external_force& E = M->external[e];
+        if (E.kind != MH_EXT_TABLE) {   // a contact: its parameter block
+            if (E.force_col >= 0 && (int64_t)E.force_col + MH_CONTACT_PARAMS <= M->ncoefs && M->table_coefs)
+                h = fnv1a(h, M->table_coefs + E.force_col, sizeof(double) * MH_CONTACT_PARAMS);
+            continue;
+        }
+        const int t = E.table;
         if (t < 0 || t >= M->ntables) continue;
         const int32_t shape[2] = {M->tables[t].degree, M->tables[t].ncol};
         h = fnv1a(h, shape, sizeof shape);
@@ -4105,6 +4133,16 @@ extern "C" int mh_eval_metabolics(mh_ctx* c, int32_t nterms, const int32_t* inde
             });
 }
 
+extern "C" int mh_eval_contact_forces(mh_ctx* c, int32_t np, const double* inputs, double* out) {
+    if (!c || !inputs || !out) return set_err(MH_ERR_INVALID, "bad argument");
+    if (np <= 0) return set_err(MH_ERR_INVALID, "mh_eval_contact_forces: %d rows", np);
+    if (c->NPAR > 0) return set_err(MH_ERR_UNSUPPORTED, "mh_eval_contact_forces with MocoParameters");
+    if (c->ncontacts == 0) return MH_OK;
+    HIPCHK(hipSetDevice(c->device));
+    return run_probe(c, inputs, (size_t)np * (1 + c->NI), out, (size_t)np * c->ncontacts * 9,
+            [&](const double* din, double* dout) { contact_forces_probe(c, np, din, dout); return MH_OK; });
+}
+
 // Path-constraint values of np probe rows [t, states, controls, ...]
 // (sparsity detection of the path-constraint callbacks).
 __global__ void __launch_bounds__(256) k_path_probe(PathEqs P, int np, int NS, int W,
@@ -4569,8 +4607,9 @@ static const Backend* select_backend(mh_ctx* c, const mh_problem* p) {
     // mh_create)
     // MocoParameters write model properties a generated back end folds into
     // its constant pool, and SpringGeneralizedForce is not in the generated
-    // code: both run on the generic interpreter
-    if (!generic && c->NPAR == 0 && c->nsprings == 0) {
+    // code, nor are the station-plane contact forces: all run on the generic
+    // interpreter
+    if (!generic && c->NPAR == 0 && c->nsprings == 0 && c->ncontacts == 0) {
         for (auto entry : kGeneratedModels) {
             const GenEntry& e = entry();
             if (e.implicit != (c->NMB > 0) || e.prescribed != (c->presc != 0)) continue;

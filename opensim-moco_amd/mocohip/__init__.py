@@ -4,9 +4,9 @@ The product is libmocohip.so (C ABI, include/mocohip.h); this package is the
 host-side mirror of the reference's MocoProblem / MocoSolver interface and
 the model compiler that feeds the C ABI.
 """
-from .model import (Axis, Bhargava2004Metabolics, Body, Coordinate, CoordinateActuator, DataTable,  # noqa: F401
-                    DeGrooteFregly2016Muscle, ExternalForce, Function, Joint,
-                    Model, PathPoint)
+from .model import (AckermannVanDenBogert2010Force, Axis, Bhargava2004Metabolics, Body, Coordinate,  # noqa: F401
+                    CoordinateActuator, DataTable, DeGrooteFregly2016Muscle, EspositoMiller2018Force, ExternalForce,
+                    Function, Joint, MeyerFregly2016Force, Model, PathPoint, Station)
 from .problem import (MocoAccelerationTrackingGoal, MocoAngularVelocityTrackingGoal, MocoBounds, MocoControlGoal,  # noqa: F401
                       MocoFinalTimeGoal, MocoJointReactionGoal, MocoOrientationTrackingGoal, MocoOutputGoal, MocoProblem, MocoStateTrackingGoal,
                       MocoSumSquaredStateGoal, MocoTranslationTrackingGoal)

@@ -104,7 +104,14 @@ class mh_table(C.Structure):
 
 class mh_external_force(C.Structure):
     _fields_ = [("body", i32), ("table", i32), ("force_col", i32),
-                ("point_col", i32), ("torque_col", i32), ("reserved", i32)]
+                ("point_col", i32), ("torque_col", i32), ("kind", i32)]
+
+
+# mh_external_kind: a table-driven force, or a station-plane contact force whose
+# force_col is the offset into table_coefs of MH_CONTACT_PARAMS doubles
+MH_EXT_TABLE, MH_EXT_CONTACT_ACKERMANN_VAN_DEN_BOGERT, MH_EXT_CONTACT_ESPOSITO_MILLER, \
+    MH_EXT_CONTACT_MEYER_FREGLY = 0, 1, 2, 3
+MH_CONTACT_PARAMS = 8
 
 
 MH_KC_COORDINATE_COUPLER = 0
@@ -272,6 +279,7 @@ MOCOHIP_SYMBOLS = {
     "mh_eval_frame_accelerations": (i32, [C.c_void_p, i32, i32, P(f64), P(f64)]),
     "mh_eval_muscle_outputs": (i32, [C.c_void_p, i32, P(i32), P(i32), i32, P(f64), P(f64)]),
     "mh_eval_metabolics": (i32, [C.c_void_p, i32, P(i32), P(i32), P(f64), i32, P(f64), P(f64)]),
+    "mh_eval_contact_forces": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
     "mh_eval_path": (i32, [C.c_void_p, i32, P(f64), P(f64)]),
     "mh_set_timing": (i32, [C.c_void_p, i32]),
     "mh_get_backend_flags": (i32, [C.c_void_p, C.c_char_p, i32]),
@@ -424,7 +432,8 @@ def _fnv1a(h: int, data: bytes) -> int:
 def model_hash(m: "mh_model") -> int:
     """mh_model_hash (mocohip.hip model_hash) restated on the host: FNV-1a
     64 over the model tape's counts, gravity, bodies, axes, functions, knots,
-    muscles, path points, actuators, external loads and their tables' shapes
+    muscles, path points, actuators, external loads and their tables' shapes,
+    contact forces and their parameter blocks
     (the keys of the generated back ends; tests/test_abi.py checks it against
     the library)."""
     h = 1469598103934665603
@@ -442,7 +451,13 @@ def model_hash(m: "mh_model") -> int:
                       (m.external, mh_external_force, m.nexternal)):
         h = _fnv1a(h, arr(ptr, T, n))
     for e in range(m.nexternal):
-        t = m.external[e].table
+        E = m.external[e]
+        if E.kind != MH_EXT_TABLE:   # a contact: its parameter block
+            if E.force_col >= 0 and E.force_col + MH_CONTACT_PARAMS <= m.ncoefs and m.table_coefs:
+                h = _fnv1a(h, C.string_at(C.addressof(m.table_coefs.contents) + 8 * E.force_col,
+                                          8 * MH_CONTACT_PARAMS))
+            continue
+        t = E.table
         if 0 <= t < m.ntables:
             h = _fnv1a(h, bytes((i32 * 2)(m.tables[t].degree, m.tables[t].ncol)))
     if m.nwraps > 0 or m.npathwraps > 0:

@@ -946,6 +946,9 @@ class _Emitter:
         for ie, e in enumerate(M.ext):
             if only is not None and ie not in only:
                 continue
+            if e.kind != abi.MH_EXT_TABLE:
+                # (mh_create runs contact on the generic interpreter: select_backend)
+                raise NotImplementedError("station-plane contact forces are not in the generated code")
             b = e.body
             ti = e.table
             g.k += 1

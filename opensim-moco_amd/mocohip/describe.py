@@ -140,6 +140,11 @@ def describe(study) -> str:
     for e in m.external_forces:
         out.append(" ".join(["extforce", _s(e.name), _s(e.body), _s(e.table), _s(e.force_identifier),
                              _s(e.point_identifier), _s(e.torque_identifier)]))
+    for t in getattr(m, "stations", {}).values():
+        out.append(f"station {_s(t.name)} {_s(t.body)} {_ds(t.location)} {_s(t.path)}")
+    for f in getattr(m, "contact_forces", []):
+        out.append(" ".join(["contact", str(int(f.kind)), _s(f.name), _s(f.station), _s(f.path)]
+                            + [_d(v) for v in f.parameters()]))
     # the problem
     out.append(" ".join(["problem", _bounds(p.time_initial), _bounds(p.time_final),
                          _bounds(p.default_speed_bounds), str(int(bool(p.bound_activation_from_excitation))),

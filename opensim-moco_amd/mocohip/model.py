@@ -327,6 +327,74 @@ class ExternalForce:
 
 
 @dataclass
+class Station:
+    """OpenSim Station: a point fixed in a body (``location`` in the body's
+    frame).  Path ``/<name>`` unless given."""
+    name: str
+    body: str
+    location: Sequence[float] = (0.0, 0.0, 0.0)
+    path: str = ""
+
+
+@dataclass
+class AckermannVanDenBogert2010Force:
+    """StationPlaneContactForce.h AckermannVanDenBogert2010Force (properties
+    and defaults of its constructProperties): compliant contact of a station
+    with the ground plane y = 0, friction along ground x."""
+    name: str
+    station: str
+    stiffness: float = 5e7
+    dissipation: float = 1.0
+    friction_coefficient: float = 1.0
+    tangent_velocity_scaling_factor: float = 0.05
+    path: str = ""
+    kind = abi.MH_EXT_CONTACT_ACKERMANN_VAN_DEN_BOGERT
+
+    def parameters(self) -> List[float]:
+        return [float(self.stiffness), float(self.dissipation), float(self.friction_coefficient),
+                float(self.tangent_velocity_scaling_factor), 0.0]
+
+
+@dataclass
+class EspositoMiller2018Force:
+    """StationPlaneContactForce.h EspositoMiller2018Force: the smooth
+    in / out-of-contact transition with the spring's resting length
+    ``depth_offset``."""
+    name: str
+    station: str
+    stiffness: float = 2.0e6
+    dissipation: float = 1.0
+    friction_coefficient: float = 1.0
+    tangent_velocity_scaling_factor: float = 0.05
+    depth_offset: float = 0.001
+    path: str = ""
+    kind = abi.MH_EXT_CONTACT_ESPOSITO_MILLER
+
+    def parameters(self) -> List[float]:
+        return [float(self.stiffness), float(self.dissipation), float(self.friction_coefficient),
+                float(self.tangent_velocity_scaling_factor), float(self.depth_offset)]
+
+
+@dataclass
+class MeyerFregly2016Force:
+    """StationPlaneContactForce.h MeyerFregly2016Force (the friction
+    coefficient is fixed at 1 and the latch velocity at 0.05 m/s there)."""
+    name: str
+    station: str
+    stiffness: float = 1e4
+    dissipation: float = 1e-2
+    tscale: float = 1.0
+    path: str = ""
+    kind = abi.MH_EXT_CONTACT_MEYER_FREGLY
+
+    def parameters(self) -> List[float]:
+        return [float(self.stiffness), float(self.dissipation), 1.0, 0.05, float(self.tscale)]
+
+
+CONTACT_FORCE_TYPES = (AckermannVanDenBogert2010Force, EspositoMiller2018Force, MeyerFregly2016Force)
+
+
+@dataclass
 class CoordinateCouplerConstraint:
     """OpenSim CoordinateCouplerConstraint with one independent coordinate:
     q[dependent] = scale_factor * function(q[independent]) (the Simbody
@@ -488,6 +556,8 @@ class Model:
         self.wraps: Dict[str, WrapCylinder] = {}
         self.springs: List[SpringGeneralizedForce] = []
         self.offset_frames: Dict[str, OffsetFrame] = {}   # by path
+        self.stations: Dict[str, Station] = {}  # by path
+        self.contact_forces: List[object] = []  # the StationPlaneContactForce classes, in the order added
 
     # building ---------------------------------------------------------------
     def add_body(self, body: Body):
@@ -527,6 +597,52 @@ class Model:
     def add_external_force(self, e: ExternalForce):
         self.external_forces.append(e)
         return e
+
+    def add_station(self, st: Station):
+        if st.body not in self.bodies:
+            raise ValueError(f"station '{st.name}': no body '{st.body}'")
+        if not st.path:
+            st.path = "/" + st.name
+        self.stations[st.path] = st
+        return st
+
+    def find_station(self, path: str) -> Optional[Station]:
+        """The station with that path (``/<name>``, ``/componentset/<name>``
+        or ``/bodyset/<body>/<name>``) or name; None when there is none."""
+        for st in self.stations.values():
+            if path in (st.path, st.name, "/componentset/" + st.name, f"/bodyset/{st.body}/{st.name}"):
+                return st
+        return None
+
+    def add_contact_force(self, f):
+        """A StationPlaneContactForce (AckermannVanDenBogert2010Force,
+        EspositoMiller2018Force or MeyerFregly2016Force) on a station of the
+        model.  ValueError for an unknown station, a name used twice, a
+        non-positive tangent velocity scaling factor or a negative
+        depth_offset."""
+        if not isinstance(f, CONTACT_FORCE_TYPES):
+            raise TypeError(f"not a station-plane contact force: {type(f).__name__}")
+        if self.find_station(f.station) is None:
+            raise ValueError(f"contact force '{f.name}': no station '{f.station}' in the model")
+        if any(g.name == f.name for g in self.contact_forces):
+            raise ValueError(f"contact force name '{f.name}' is used twice")
+        if not isinstance(f, MeyerFregly2016Force) and not float(f.tangent_velocity_scaling_factor) > 0.0:
+            raise ValueError(f"contact force '{f.name}': tangent_velocity_scaling_factor = "
+                             f"{f.tangent_velocity_scaling_factor} is not positive")
+        if isinstance(f, EspositoMiller2018Force) and not float(f.depth_offset) >= 0.0:
+            raise ValueError(f"contact force '{f.name}': depth_offset = {f.depth_offset} is negative")
+        if not f.path:
+            f.path = f"/forceset/{f.name}"
+        self.contact_forces.append(f)
+        return f
+
+    def find_contact_force(self, path: str):
+        """(index among the contact forces, force) by path or name; None when
+        there is none."""
+        for i, f in enumerate(self.contact_forces):
+            if path in (f.path, f.name, "/" + f.name):
+                return i, f
+        return None
 
     def add_constraint(self, k: CoordinateCouplerConstraint):
         self.constraints.append(k)
@@ -952,6 +1068,19 @@ class CompiledModel:
             es.torque_col = col3(e.torque_identifier)
             ext.append(es)
 
+        # station-plane contact forces: records after the table-driven ones,
+        # parameter blocks after all table coefficients (include/mocohip.h)
+        for f in model.contact_forces:
+            st = model.find_station(f.station)
+            es = abi.mh_external_force()
+            es.body = body_index[st.body]
+            es.table = es.point_col = es.torque_col = -1
+            es.force_col = len(coefs)
+            es.kind = f.kind
+            coefs.extend([float(v) for v in st.location] + f.parameters())
+            ext.append(es)
+        self.ncontacts = len(model.contact_forces)
+
         self._bodies = _arr(abi.mh_body, bodies)
         self._axes = _arr(abi.mh_axis, axes)
         self._funcs = _arr(abi.mh_function, funcs)
@@ -1086,6 +1215,11 @@ def model_to_dict(m: Model) -> dict:
         "springs": [{"name": f.name, "coordinate": f.coordinate, "stiffness": f.stiffness,
                      "rest_length": f.rest_length, "viscosity": f.viscosity, "path": f.path}
                     for f in m.springs],
+        **({"stations": [{"name": t.name, "body": t.body, "location": list(t.location), "path": t.path}
+                         for t in m.stations.values()]} if m.stations else {}),
+        **({"contact_forces": [{"type": type(f).__name__,
+                                **{k: getattr(f, k) for k in f.__dataclass_fields__}}
+                               for f in m.contact_forces]} if m.contact_forces else {}),
         **({"offset_frames": [{"name": f.name, "body": f.body, "translation": list(f.translation),
                                **({"orientation": list(f.orientation)} if f.oriented() else {})}
                               for f in m.offset_frames.values()]} if m.offset_frames else {}),
@@ -1127,6 +1261,11 @@ def model_from_dict(d: dict) -> Model:
     for f in d.get("springs", []):
         m.add_spring(SpringGeneralizedForce(f["name"], f["coordinate"], f["stiffness"], f["rest_length"],
                                             f["viscosity"], f.get("path", "")))
+    for t in d.get("stations", []):
+        m.add_station(Station(t["name"], t["body"], tuple(t["location"]), t.get("path", "")))
+    for f in d.get("contact_forces", []):
+        cls = {c.__name__: c for c in CONTACT_FORCE_TYPES}[f["type"]]
+        m.add_contact_force(cls(**{k: v for k, v in f.items() if k != "type"}))
     for f in d.get("offset_frames", []):
         m.add_offset_frame(f["name"], f["body"], tuple(f["translation"]), tuple(f.get("orientation", (0.0, 0.0, 0.0))))
     return m

@@ -4,7 +4,9 @@ Reads the subset of OpenSim 3.x (Version 30000, joints nested in bodies) and
 4.x (JointSet with offset frames) XML that the collocation hot path needs:
 bodies, Pin/Slider/Planar/Weld/CustomJoint with Constant / LinearFunction /
 SimmSpline / MultiplierFunction transform axes, muscles with PathPoint /
-ConditionalPathPoint / MovingPathPoint geometry, CoordinateActuators.
+ConditionalPathPoint / MovingPathPoint geometry, CoordinateActuators, Stations
+and the station-plane contact forces (AckermannVanDenBogert2010Force,
+EspositoMiller2018Force, MeyerFregly2016Force).
 
 Muscles are converted to DeGrooteFregly2016Muscle exactly as
 DeGrooteFregly2016Muscle::replaceMuscles does
@@ -21,7 +23,7 @@ from typing import Dict, List, Optional
 from . import abi
 from .model import (Axis, Body, Coordinate, CoordinateActuator,
                     CoordinateCouplerConstraint, DeGrooteFregly2016Muscle,
-                    Function, Joint, Model, PathPoint, WrapCylinder)
+                    Function, Joint, Model, PathPoint, Station, WrapCylinder)
 
 # opensim-core Millard2012EquilibriumMuscle defaults (restated).
 MILLARD_DEFAULTS = dict(fiber_damping=0.1, default_activation=0.05,
@@ -328,6 +330,12 @@ def read_osim(path: str, remove_muscles: bool = False,
                                   _axes_for(jel, jel.tag, coords), pl, po, cl, co))
     for k in _constraints(mel):
         model.add_constraint(k)
+    # stations, wherever they are (the model's components, a ComponentSet, a
+    # body's components): the contact forces below name them
+    for st in mel.iter("Station"):
+        frame = _text(st, "socket_parent_frame") or _text(st, "socket_parent_frame_connectee_name") or ""
+        model.add_station(Station(st.get("name"), frame.strip().split("/")[-1],
+                                  tuple(_floats(_text(st, "location", "0 0 0")))))
     # forces, in force-set order
     fs = mel.find("ForceSet/objects")
     if fs is not None:
@@ -344,6 +352,8 @@ def read_osim(path: str, remove_muscles: bool = False,
                     _float(f, "optimal_force", 1.0),
                     _float(f, "min_control", -math.inf),
                     _float(f, "max_control", math.inf)))
+            elif f.tag in CONTACT_TAGS:
+                model.add_contact_force(_contact_force(f))
             else:
                 raise NotImplementedError(f"force {f.tag} not supported on the hot path")
     # the metabolics components of <components> (a model's own list) and of
@@ -353,7 +363,27 @@ def read_osim(path: str, remove_muscles: bool = False,
         for comp in (list(el) if el is not None else []):
             if comp.tag == "Bhargava2004Metabolics":
                 model.add_component(_metabolics(comp))
+            elif comp.tag in CONTACT_TAGS:
+                model.add_contact_force(_contact_force(comp))
+            elif comp.tag == "SmoothSphereHalfSpaceForce":
+                raise NotImplementedError(f"force {comp.tag} not supported on the hot path")
     return model
+
+
+CONTACT_TAGS = ("AckermannVanDenBogert2010Force", "EspositoMiller2018Force", "MeyerFregly2016Force")
+
+
+def _contact_force(el):
+    """A station-plane contact force element: its station socket
+    (socket_station or socket_station_connectee_name) and the properties of
+    its class; absent ones keep the reference's defaults."""
+    from . import model as _m
+    station = (_text(el, "socket_station") or _text(el, "socket_station_connectee_name") or "").strip()
+    f = getattr(_m, el.tag)(el.get("name"), station)
+    for prop in f.__dataclass_fields__:
+        if prop not in ("name", "station", "path"):
+            setattr(f, prop, _float(el, prop, getattr(f, prop)))
+    return f
 
 
 def _metabolics(el):

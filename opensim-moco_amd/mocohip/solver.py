@@ -694,6 +694,43 @@ class HipNLP(_NLPBase):
                 got = self.eval_metabolics(comp, np.column_stack([t, self.point_inputs(x)]))
                 labels += [own[i] for i in keep]
                 vals = np.column_stack([vals, got[:, keep]])
+        # the contact forces' force_on_station outputs, after those
+        own, got = self.contact_forces(x, paths)
+        labels += own
+        vals = np.column_stack([vals, got])
+        return (t, labels, vals) if with_times else (labels, vals)
+
+    def eval_contact_forces(self, inputs: np.ndarray) -> np.ndarray:
+        """Rows [t, point inputs] (as eval_dae) -> [rows, contacts, 9]: for
+        each station-plane contact force of the model, in the order added, the
+        force on the body at the station in ground (3), the station's position
+        in ground (3) and its velocity in ground (3) (mh_eval_contact_forces)."""
+        inputs = np.ascontiguousarray(inputs, float)
+        assert inputs.ndim == 2 and inputs.shape[1] == 1 + self.NI
+        npts, nc = inputs.shape[0], len(self.rep.problem.model.contact_forces)
+        out = np.empty((max(npts, 1), max(nc, 1), 9))
+        self._check(self._fn("eval_contact_forces")(self.ctx, npts, abi.dptr(inputs), abi.dptr(out)))
+        return out[:npts, :nc]
+
+    def contact_forces(self, trajectory, paths, with_times: bool = False):
+        """(labels, values [grid points, len(labels)]), shaped as
+        muscle_outputs: for every contact force whose output path
+        "<force path>|force_on_station" matches one of the regular expressions
+        ``paths``, the three columns "<that path>_x", "_y", "_z" of the force
+        on the station in ground at every grid point of ``trajectory``."""
+        import re
+        from .trajectory import nlp_grid
+        model = self.rep.problem.model
+        pats = [re.compile(p) for p in paths]
+        x = trajectory.to_iterate(self) if hasattr(trajectory, "to_iterate") else np.asarray(trajectory, float)
+        t = x[0] + (x[1] - x[0]) * nlp_grid(self)
+        keep = [i for i, f in enumerate(model.contact_forces)
+                if any(p.fullmatch(f"{f.path}|force_on_station") for p in pats)]
+        labels = [f"{model.contact_forces[i].path}|force_on_station_{a}" for i in keep for a in "xyz"]
+        vals = np.zeros((len(t), 0))
+        if keep:
+            got = self.eval_contact_forces(np.column_stack([t, self.point_inputs(x)]))
+            vals = got[:, keep, :3].reshape(len(t), 3 * len(keep))
         return (t, labels, vals) if with_times else (labels, vals)
 
     def eval_metabolics(self, component, inputs: np.ndarray) -> np.ndarray:
@@ -837,6 +874,9 @@ class OracleNLP(_NLPBase):
     prefix = "orc_"
 
     def __init__(self, rep: ProblemRep, opts: abi.mh_options, threads: int = 1):
+        if getattr(rep.problem.model, "contact_forces", None):
+            raise TypeError("OracleNLP: the model has station-plane contact forces, which the CPU oracle does not "
+                            "evaluate (it would drop them)")
         self.lib = abi.load_oracle()
         super().__init__(rep, opts)
         self.lib.orc_set_threads(self.ctx, int(threads))
@@ -973,8 +1013,10 @@ class MocoStudy:
         trajectory's times and one column per matching output, labelled with
         the output's path; trajectory.write_table / read_table store it as an
         .sto file.  The outputs are those of the problem's
-        DeGrooteFregly2016Muscles (HipNLP.muscle_outputs); prescribed
-        kinematics are applied, parameters are not."""
+        DeGrooteFregly2016Muscles and Bhargava2004Metabolics components and the
+        contact forces' "<force path>|force_on_station" (three columns, suffixes
+        _x, _y, _z) (HipNLP.muscle_outputs); prescribed kinematics are applied,
+        parameters are not."""
         own = nlp is None
         nlp = nlp or self.create_nlp()
         if not hasattr(nlp, "muscle_outputs"):
